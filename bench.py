@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """Benchmark of the Allegro hot path (forward + forces) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c3|c2|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c3|c2|c5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (metric, value, ms_per_step, ...).  `--full` adds
+everything else the line can carry, each part measured after the timed steps: the sustained run, the per-launch HIP-event
+profile and rooflines, the device neighbour list, the MD loop, the CPU and GPU baselines of the oracle port with the parity
+sample, and the secondary C3 / C5 records.  `--dump-outputs DIR` writes what the last timed step computed (atomic_energy.npy,
+forces.npy) for output-for-output comparisons of two builds; the inputs are the same from run to run.
 
 A "step" is one pass of the hot path (energies + forces of every atom) over one synthetic periodic
 box held resident in HBM; the neighbor list / CSR build is outside the timed region.
@@ -399,6 +405,46 @@ def secondary_workload(name, dev, steps, warmup, cpu_edges):
     return rec
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, out, own_ids, n_atoms, dist, rank):
+    """--dump-outputs: (E_i, forces) of the last timed step as out_dir/atomic_energy.npy [N] and out_dir/forces.npy [N,3] in the
+    model dtype (float32 / float64), atoms in the order of the generated box.  Sharded runs: every rank's owned rows (`own_ids`: their
+    atom ids) are gathered on rank 0.  Above DUMP_MAX_BYTES a fixed, seeded sample of atoms is written instead, their ids (as
+    float64) in out_dir/sample_rows.npy."""
+    e, f = (t.detach().cpu().numpy() for t in out)
+    if own_ids is not None:
+        parts = [(np.asarray(own_ids), e, f)]
+        if dist is not None:
+            parts = [None] * dist.get_world_size()
+            dist.all_gather_object(parts, (np.asarray(own_ids), e, f))
+        if rank != 0:
+            return
+        e_all = np.zeros(n_atoms, dtype=e.dtype)
+        f_all = np.zeros((n_atoms, 3), dtype=f.dtype)
+        seen = np.zeros(n_atoms, dtype=np.int64)
+        for ids, ee, ff in parts:
+            e_all[ids], f_all[ids] = ee, ff
+            seen[ids] += 1
+        if not (seen == 1).all():
+            raise RuntimeError("--dump-outputs: the shards' owned atoms do not partition the box")
+        e, f = e_all, f_all
+    elif rank != 0:
+        return
+    if e.shape != (n_atoms,) or f.shape != (n_atoms, 3):
+        raise RuntimeError(f"--dump-outputs: unexpected output shapes {e.shape} / {f.shape} for {n_atoms} atoms")
+    arrays = {"atomic_energy": e, "forces": f}
+    row_bytes = e.itemsize + 3 * f.itemsize
+    if n_atoms * row_bytes > DUMP_MAX_BYTES:
+        k = DUMP_MAX_BYTES // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(n_atoms, size=k, replace=False))
+        arrays = {"atomic_energy": e[rows], "forces": f[rows], "sample_rows": rows.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 KB_EV = 8.617333262e-5     # eV / K
 ACC_UNIT = 9.64853321e-3   # (eV / A / amu) in A / fs^2
 
@@ -710,6 +756,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="c4", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need (sustained run, profile / rooflines, neighbour list, MD loop, "
+                         "CPU / GPU baselines with the parity sample, secondary workloads); the --no-* switches below thin this out")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the per-atom energies and forces of the last timed step to DIR/<name>.npy (at most 64 MB: a fixed, "
+                         "seeded sample of rows beyond that, with their atom ids in DIR/sample_rows.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-gpu-reference", action="store_true", help="skip the eager PyTorch-ROCm oracle path on the GPU")
@@ -717,7 +769,8 @@ def main():
     ap.add_argument("--sustain", type=float, default=8.0,
                     help="seconds of additional back-to-back steps AFTER the timed region (reported as config.sustained): "
                          "long enough for an external sampler (rocm-smi every few seconds) to witness the GPU busy; 0 = off")
-    ap.add_argument("--stages", action="store_true", help="also print every launch of one step with its HIP-event time")
+    ap.add_argument("--stages", action="store_true",
+                    help="also print every launch of one step with its HIP-event time (runs the profile pass, also without --full)")
     ap.add_argument("--no-md", action="store_true", help="skip the short NVE loop (config.md_loop: measured ns/day incl. neighbour lists)")
     ap.add_argument("--no-secondary", action="store_true",
                     help="default C4 line only: skip the compact C3 / C5 records (`secondary`: ms/step, roofline fraction, parity sample)")
@@ -736,6 +789,10 @@ def main():
                     help="step: the whole hot path (default, the driver's contract); train-op: training step of the operator seam; "
                          "train-step: optimisation step of the whole model in training mode")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.mode != "step" or args.shard_sweep or args.emulate_shard):
+        raise SystemExit("bench.py: --dump-outputs writes the outputs of the whole box: --mode step without --shard-sweep / --emulate-shard")
     if args.mode == "train-op":
         assert torch.cuda.is_available(), "bench.py needs a GPU (no CPU fallback)"
         dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
@@ -995,7 +1052,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
     torch.cuda.synchronize()
     dt_rank = time.perf_counter() - t0  # this rank's own K steps (its waits inside the collectives included), before the closing barrier
     if dist is not None:
@@ -1015,10 +1072,16 @@ def main():
         rank_ms = {"max": float(tr.max()), "mean": float(tr.mean()), "min": float(tr.min()), "per_rank": [round(float(x), 4) for x in tr],
                    "edges_per_rank": [int(x) for x in ne]}
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs:
+        # (outside the clock, before anything else runs a step: the results may be views of buffers the next step overwrites)
+        own_ids = None
+        if halo:
+            own_ids = np.nonzero(mine)[0] if owned_mode else shard.owned_ids().cpu().numpy()
+        dump_outputs(args.dump_outputs, out, own_ids, N, dist, rank)
     # sustained run (outside the timed region, same step): the K-step region of the contract is ~0.2 s at C4, too short
     # for an independent utilisation sampler; all ranks take part so the collective pattern is the same
     sustained = None
-    if args.sustain > 0 and not args.emulate_shard:
+    if args.full and args.sustain > 0 and not args.emulate_shard:
         n_sus = max(args.steps, int(args.sustain / max(dt / args.steps, 1e-6)))
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -1064,7 +1127,7 @@ def main():
             line["config"]["sustained"] = sustained
         if rank_ms is not None:
             line["config"]["rank_ms_per_step"] = rank_ms
-        if not args.no_profile:
+        if (args.full or args.stages) and not args.no_profile:
             if halo and shard is not None and pos_local is None:
                 pos_local = shard._buffers(dtype, dev)[0]  # (owned + ghost rows as the last timed step left them)
             stages = profile_stages(model, pos if shard is None else (pos_local if halo else pos.index_select(0, shard.local_ids)), graph)
@@ -1093,7 +1156,7 @@ def main():
                 for nm, ms, nb, fl in stages:
                     print(f"[stage] {nm:24s} {ms * 1e3:9.1f} us {nb / max(ms, 1e-9) / 1e6:8.0f} GB/s (algorithmic)"
                           f"{fl / max(ms, 1e-9) / 1e9:8.1f} TFLOP/s", file=sys.stderr)
-        if world == 1 and g is not None and g.cell is not None:
+        if args.full and world == 1 and g is not None and g.cell is not None:
             # reported separately, never part of `value`: the on-device cell-list build of the same graph
             from allegro_amd.nn import neighbor_list
 
@@ -1116,23 +1179,24 @@ def main():
             torch.cuda.synchronize()
             line["config"]["neighbor_list_device_ms"]["list"] = (time.perf_counter() - t1) * 1e3
             del nl_graph
-        if world == 1 and g is not None and g.cell is not None and WORKLOADS[args.workload]["kind"] == "si" and not args.no_md and not args.emulate_shard:
+        if (args.full and world == 1 and g is not None and g.cell is not None and WORKLOADS[args.workload]["kind"] == "si" and not args.no_md
+                and not args.emulate_shard):
             # the metric's "ns/day for the box" as a measured LOOP (never `value`): list + preparation + hot path + integrator, 40 steps
             md = md_loop(model, pos, types, torch.tensor(g.cell, dtype=torch.float64), float(cfg["r_max"]), steps=40, warmup=5)
             line["config"]["md_loop"] = {k: md[k] for k in ("steps", "dt_fs", "temperature_K", "list_rebuilds", "max_degree_seen", "ms_per_md_step",
                                                             "ms_per_md_step_median", "ns_per_day", "includes", "max_abs_drift_eV",
                                                             "mean_kinetic_eV", "drift_over_mean_kinetic")}
         parity_failed = False
-        if world == 1 and not args.no_cpu_baseline and g is not None:
+        if args.full and world == 1 and not args.no_cpu_baseline and g is not None:
             # ~20 s of CPU work for the headline model; the l_max=3 fp64 stack is ~10x heavier per edge
             line["cpu_baseline"], line["parity_sample"] = cpu_baseline(g, cfg, model,
                                                                        target_edges=180000 if cfg["l_max"] <= 2 else 24000)
             parity_failed = not line["parity_sample"]["ok"]
-        if world == 1 and not args.no_gpu_reference and not args.emulate_shard and g is not None:
+        if args.full and world == 1 and not args.no_gpu_reference and not args.emulate_shard and g is not None:
             line["gpu_reference_baseline"] = gpu_reference_baseline(g, cfg, model, dev,
                                                                     target_edges=60000 if cfg["l_max"] <= 2 else 12000)
             line["speedup_vs_gpu_reference"] = line["value"] / line["gpu_reference_baseline"]["value"]
-        if (world == 1 and args.workload == "c4" and not args.no_secondary and not args.no_cpu_baseline and not args.emulate_shard
+        if (args.full and world == 1 and args.workload == "c4" and not args.no_secondary and not args.no_cpu_baseline and not args.emulate_shard
                 and not os.environ.get("AA_BENCH_CELLS")):
             # the other BASELINE workloads in front of the driver: same model family at 10^4 atoms (C3), and the
             # fp64 / l_max 3 / 3-layer / 128-feature / 2-species water box (C5) with its own kernel family

@@ -1,11 +1,11 @@
 #!/bin/bash
 # Run ON THE GPU BOX (via gpurun): rocprofv3 kernel-trace stats + separate PMC passes of bench.py.
-# Usage: tools/profile_gpu.sh <workload> <tag>
+# Usage: tools/profile_gpu.sh <workload> <tag> [results folder, relative to the repository root; default results]
 set -u
 WL=${1:-c3}; TAG=${2:-r01}
 export TMPDIR=/tmp
 ROOT=$(pwd)
-OUT=$ROOT/gpurun_out/prof_${TAG}_${WL}
+OUT=$ROOT/${3:-results}/prof_${TAG}_${WL}
 mkdir -p $OUT
 CMD="python $ROOT/bench.py --workload $WL --steps 5 --warmup 2 --no-cpu-baseline --no-profile --no-gpu-reference --sustain 0"
 cd /tmp
