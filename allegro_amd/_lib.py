@@ -41,7 +41,7 @@ class PlanOptions(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "tp_generic", "tp_no_chain", "tp_no_moments", "tp_no_operator", "tp_force_operator", "tp_operator_fused",
         "gemm_no_chain", "gemm_fp32_mfma", "gemm_valu", "gemm_v1", "gemm_lds_epilogue", "f64_column_loop",
-        "embed_no_fuse", "fused_forward", "fused_recompute_w0", "moments_waves_per_block", "f64_rows", "no_channel_padding", "fused_tail", "fused_keep_split", "poison_workspace", "no_slot_form", "op_proj_gemm", "op_env_vector", "staged_no_fold", "op_recompute_bvecs", "readout_two_pass", "tp_prefer_moments", "fused_narrow", "chain_staged_weights")]
+        "embed_no_fuse", "fused_forward", "moments_waves_per_block", "f64_rows", "no_channel_padding", "poison_workspace", "no_slot_form", "op_proj_gemm", "op_env_vector", "staged_no_fold", "op_recompute_bvecs", "readout_two_pass", "tp_prefer_moments", "fused_narrow", "chain_staged_weights")]
 
 
 def options_from_env() -> PlanOptions:
@@ -58,11 +58,8 @@ def options_from_env() -> PlanOptions:
     o.f64_column_loop = {"0": 1, "2": 2}.get(env.get("AA_F64_NLOOP", "1")[:1], 0)
     o.embed_no_fuse = flag("AA_EMBED_NOFUSE")
     o.fused_forward = {"0": 3, "1": 1, "2": 2, "4": 4}.get(env.get("AA_FUSED", "")[:1], 0)  # unset: automatic; 2 / 4: pure team / mixed form for every graph with segments <= 128 (A/B)
-    o.fused_recompute_w0 = flag("AA_FUSED_RECOMPUTE")
     o.moments_waves_per_block = int(env.get("AA_MOM_WPB", "0") or 0)
     o.no_channel_padding = flag("AA_NO_PAD")
-    o.fused_tail = {"1": 1, "2": 2}.get(env.get("AA_FUSED_TAIL", "")[:1], 0)  # experimental builds only (AA_BUILD_EXPERIMENTAL=1)
-    o.fused_keep_split = int(os.environ.get("AA_FUSED_KEEP", "0") or 0)  # A/B: 1 none, 2 two-body, 3 two-body + lat0 (0: default)
     o.no_slot_form = flag("AA_NO_SLOT_FORM")  # A/B: the unfolded single-layer pipeline on operator-kernel plans
     o.op_proj_gemm = {"1": 1, "0": 2}.get(env.get("AA_OP_PROJ", "")[:1], 0)  # env projections of the operator kernels as batched GEMMs: 1 always, 0 never
     o.op_env_vector = flag("AA_OP_ENV_VECTOR")  # A/B: vector form of tp_op_edge_env in fp64
@@ -70,7 +67,7 @@ def options_from_env() -> PlanOptions:
     o.op_recompute_bvecs = flag("AA_OP_RECOMPUTE_BVECS")  # A/B: tp_op_bvecs_kernel in the layer-0 reverse
     o.readout_two_pass = flag("AA_READOUT_TWO_PASS")  # A/B: readout_backward_kernel instead of the fused energy + slope pass
     o.tp_prefer_moments = flag("AA_TP_PREFER_MOM")  # A/B: the round-4 selection (moments kernels) where the operator kernels are now preferred
-    o.fused_narrow = {"1": 1, "2": 2, "3": 3, "5": 5, "6": 6, "7": 7}.get(env.get("AA_FUSED_NARROW", "")[:1], 0)  # A/B: 1 = the one-wave-per-SIMD fused forward, 2 = the eight-wave lock-step form, 3 = the four-wave form on small boxes too, 5 = ... with the env projections on the matrix cores
+    o.fused_narrow = {"1": 1, "2": 2, "3": 3}.get(env.get("AA_FUSED_NARROW", "")[:1], 0)  # A/B: 1 = the one-wave-per-SIMD fused forward, 2 = the eight-wave form (+ tail) at any size, 3 = the four-wave form at any size
     o.chain_staged_weights = flag("AA_CHAIN_STAGED")  # A/B: the general chain kernel for the one-layer reverse chains
     o.poison_workspace = flag("AA_POISON")  # debugging: NaN-filled workspace before every step
     o.f64_rows = {"0": 2, "2": 1}.get(env.get("AA_F64_ROWS", "")[:1], 0)  # 0: off, 2: wherever applicable
@@ -272,7 +269,7 @@ LIB_NAME = "liballegro_amd.so"
 def lib_path() -> str:
     """In-tree library next to this file; ALLEGRO_AMD_LIBRARY points at another build of the same sources
     (instrumented variants of tools/)."""
-    from .build import LIB_PATH  # (liballegro_amd_experimental.so under AA_BUILD_EXPERIMENTAL=1)
+    from .build import LIB_PATH
 
     return os.environ.get("ALLEGRO_AMD_LIBRARY") or LIB_PATH
 

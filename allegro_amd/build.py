@@ -15,13 +15,6 @@ SOURCES = ["aa_gemm.hip", "aa_tp.hip", "aa_tp_spec.hip", "aa_tp_op.hip", "aa_tp_
 # tree that copy is GENERATED from <repo>/include/allegro_amd.h at build time and not tracked (tests/test_lib_symbols.py checks identity)
 INCLUDE_DIR = os.path.join(HERE, "include")
 LIB_PATH = os.path.join(HERE, "liballegro_amd.so")
-# Measured-and-rejected kernels stay out of the product library; AA_BUILD_EXPERIMENTAL=1 adds them (their own opt-in
-# switches, their own tests) so that the measurements recorded in DESIGN.md section 9 stay reproducible:
-#   aa_fused_bwd.hip  fused per-atom-tile reverse tail (aa_plan_options.fused_tail / AA_FUSED_TAIL=1), section 9.4
-EXPERIMENTAL = os.environ.get("AA_BUILD_EXPERIMENTAL", "0")[:1] == "1"
-if EXPERIMENTAL:
-    SOURCES = SOURCES[:SOURCES.index("aa_model.hip")] + ["aa_fused_bwd.hip"] + SOURCES[SOURCES.index("aa_model.hip"):]
-    LIB_PATH = os.path.join(HERE, "liballegro_amd_experimental.so")  # (never overwrites the product library)
 TORCH_LIB_PATH = os.path.join(HERE, "liballegro_amd_torch.so")  # dispatcher op for torch.export / AOTI / C++ hosts
 
 
@@ -107,7 +100,7 @@ def _object_for(src: str, header_hash: str) -> str:
     return os.path.join(OBJ_DIR, f"{os.path.splitext(src)[0]}-{h.hexdigest()[:16]}.o")
 
 
-EXTRA_DEFINES = [d for d in os.environ.get("AA_BUILD_DEFINES", "").split() if d] + (["-DAA_EXPERIMENTAL_TAIL"] if EXPERIMENTAL else [])  # e.g. "-DAA_FUSED_TIMING" (experiments)
+EXTRA_DEFINES = [d for d in os.environ.get("AA_BUILD_DEFINES", "").split() if d]  # e.g. "-DAA_FUSED_TIMING" (experiments)
 
 
 def _build_library_locked(verbose: bool) -> str:

@@ -114,7 +114,9 @@ int launch_chain_b2_resident(const ChainB2Args& g, hipStream_t stream) {
   if ((g.lda | g.ldadd | g.ldz | g.ldc0 | g.ldc1) & 3) return fail(AA_ERR_INVALID, "resident chain: row strides must be multiples of 4 floats");
   const size_t smem = sizeof(u32x4) * 4 * kWStep + sizeof(float) * 8 * 32 * kTileLdT;
   const int64_t groups = ((g.M + 31) / 32 + 7) / 8;
-  dim3 grid((unsigned)std::min<int64_t>(groups, fused_num_cus()));
+  const int cus = device_cu_count();
+  if (cus < 0) return cus;
+  dim3 grid((unsigned)std::min<int64_t>(groups, cus));
   AA_CHECK_HIP(hipFuncSetAttribute((const void*)chain_b2_resident_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(smem)));
   hipLaunchKernelGGL(chain_b2_resident_kernel, grid, dim3(512), smem, stream, g);
   AA_CHECK_HIP(hipGetLastError());

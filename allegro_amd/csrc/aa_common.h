@@ -22,6 +22,7 @@ namespace aa {
 
 void set_error(const std::string& msg);
 int fail(int code, const std::string& msg);
+int device_cu_count();  // CUs of the current device (cached per device id), or AA_ERR_HIP through fail()
 
 #define AA_CHECK_HIP(expr)                                                                      \
   do {                                                                                          \
@@ -639,67 +640,29 @@ int launch_tp_spec_bwd(int sig, const TpSpecBwdArgs& a, hipStream_t stream);
 // fused per-atom-tile kernels (aa_fused.hip): the whole forward of the standard 2-layer, 64-wide stack in ONE launch
 // ----------------------------------------------------------------------------------------------
 constexpr int kFusedMaxSteps = 56;
-constexpr int kFusedKeepDefault = 2;
-// Env projection of the fused forward, x2s[j][ch] = f sum_k M[j][k] Wenv[k][r(j)][ch], on the matrix cores: the per-atom moments
-// become an operand tile whose 32 "edge" columns are the components j, one 64x64 bf16x3 layer per irrep (2 R MFMA steps instead
-// of 4 env-weight steps of 288 FMAs each).  Built, parity-green, and measured 2.5 % SLOWER than the vector form on MI355X
-// (same-box A/B, profiles/r04_v12_ab_c4_proj_mfma.txt: fused forward 4.01 -> 4.11 ms): 12 more MFMA steps per tile cost more
-// than the 2 300 FMAs they replace.  -DAA_PROJ_MFMA builds it (A/B); the product uses the vector form.
-#ifdef AA_PROJ_MFMA
-constexpr bool kProjMfma = true;
-#else
-constexpr bool kProjMfma = false;
-#endif
-// The first layer of scalar_embed_mlp is LINEAR in the two-body embedding, and the embedding is linear in the 8 radial basis
-// functions (emb0[c] = sum_n basis[n] tab[pair][n][c], scalarembed.py:60-81 / :157-175), so its pre-activation is
-// h[k] = sum_n basis[n] T[pair][n][k] with T = tab[pair] @ W0 -- a table of the same size, folded at pack time.  The fused
-// forward then has no 64x64 layer L0 (2 of its 32 MFMA steps and 2 tile splits) and the last reverse chain no layer W0^T
-// (2 of 12 steps): d basis[n] = sum_k d_h[k] T[pair][n][k].  -DAA_NO_FOLD_EMBED builds the unfolded form (A/B).
-#ifdef AA_NO_FOLD_EMBED
-constexpr bool kFoldEmbed = false;
-#else
-constexpr bool kFoldEmbed = true;
-#endif
-// The same algebra one level up.  The OUTPUT layer of a latent ScalarMLPFunction is linear and its result only ever enters
-// linear first layers (dense-net concat, _allegro.py:272-300: lat_l is a K-block of the next latent MLP and of edge_readout),
-// so lat_l = a_l @ Wout_l never has to be formed in the forward pass: the consumers take the hidden activation a_l against
-// Wout_l @ W_in[lat_l rows], folded at pack time (fp64, then rounded once).  The fused forward loses the two 64x64 output
-// layers L4 and L7 (26 instead of 30 MFMA steps); the reverse pass only needs the stored pre-activations and is unchanged,
-// except that the readout-reverse chain merges "d lat1 = d ro_h @ Wro[lat1]^T" and "@ Wout_1^T" into one 64x64 layer.
-// -DAA_NO_FOLD_LATENT builds the unfolded form (A/B).
-#ifdef AA_NO_FOLD_LATENT
-constexpr bool kFoldLatent = false;
-#else
-constexpr bool kFoldLatent = true;
-#endif
-// The single-layer pipeline's version of all of the above for any depth ("slot form", see aa_model_plan::slot_form): run-time
-// switch aa_plan_options.no_slot_form, build-time -DAA_NO_SLOT_FORM.
-#ifdef AA_NO_SLOT_FORM
-constexpr bool kSlotForm = false;
-#else
-constexpr bool kSlotForm = true;
-#endif
-// reverse side of the lat0 fold: Wout_0^T rides in the lat0 columns of the readout-reverse chain's second layer, and what is left
-// of the output layer's reverse -- (d a_0 + d a_0 of the moments) x silu'(h) -- is the operand transform (a_mode 2) of the
-// latent-0 reverse chain, which is then ONE layer (4 steps instead of 6).  -DAA_NO_FOLD_LAT0_REV: A/B.
-#if defined(AA_NO_FOLD_LAT0_REV) || defined(AA_NO_FOLD_LATENT)
-constexpr bool kFoldLat0Rev = false;
-#else
-constexpr bool kFoldLat0Rev = true;
-#endif
-// ... and at the front: EDGE_EMBEDDING = a_e @ W1 (the linear output layer of scalar_embed_mlp, a_e = silu(h)) only ever enters
-// linear maps -- env_embed_linear / first_layer_env_embed_projection (tensorembed.py:88-89, _allegro.py:251-258) and, through
-// the moments, the env weights of layer 0.  With W1 folded into all of them (first stage: W1 @ [proj | env]; env weights:
-// W1 @ Wenv0) the fused forward has no layer L1 either (24 MFMA steps), works on a_e wherever it used the embedding and stores
-// a_e in the embedding's slot; the reverse pass that FOLLOWS A FUSED FORWARD reads a_e there: tp_mom_bwd_first with the folded
-// transposed env weights, and the last reverse chain is ONE 256 -> 64 layer ((W1 @ G0)^T, + d a_e of the moments, x silu'(h),
-// contracted against the folded two-body table).  After a staged forward (true embedding stored) the unfolded reverse runs.
-// -DAA_NO_FOLD_EMB1 builds without (A/B); the experimental reverse tail reads the true embedding: no fold there.
-#if defined(AA_NO_FOLD_EMB1) || defined(AA_NO_FOLD_EMBED) || defined(AA_EXPERIMENTAL_TAIL)
-constexpr bool kFoldEmb1 = false;
-#else
-constexpr bool kFoldEmb1 = true;
-#endif  // FusedFwdArgs::keep when aa_plan_options.fused_keep_split is 0
+constexpr int kFusedKeepDefault = 2;  // split tile pairs the one-tile form of fused_fwd_kernel holds in registers (see its KEEP)
+// The fused forward runs the FOLDED program (aa_model_plan_describe names each fold):
+//  * fold_embed_table: the first layer of scalar_embed_mlp is LINEAR in the two-body embedding, and the embedding is linear in the 8
+//    radial basis functions (emb0[c] = sum_n basis[n] tab[pair][n][c], scalarembed.py:60-81 / :157-175), so its pre-activation is
+//    h[k] = sum_n basis[n] T[pair][n][k] with T = tab[pair] @ W0 -- a table of the same size, folded at pack time.  The fused
+//    forward then has no 64x64 layer L0 and the last reverse chain no layer W0^T: d basis[n] = sum_k d_h[k] T[pair][n][k].
+//  * fold_latent_outputs: the OUTPUT layer of a latent ScalarMLPFunction is linear and its result only ever enters linear first
+//    layers (dense-net concat, _allegro.py:272-300: lat_l is a K-block of the next latent MLP and of edge_readout), so
+//    lat_l = a_l @ Wout_l is never formed in the forward pass: the consumers take the hidden activation a_l against
+//    Wout_l @ W_in[lat_l rows], folded at pack time (fp64, then rounded once).  No layers L4 / L7; the reverse pass only needs the
+//    stored pre-activations, except that the readout-reverse chain merges "d lat1 = d ro_h @ Wro[lat1]^T" and "@ Wout_1^T".
+//  * fold_lat0_reverse: Wout_0^T rides in the lat0 columns of the readout-reverse chain's second layer, and what is left of the
+//    output layer's reverse -- (d a_0 + d a_0 of the moments) x silu'(h) -- is the operand transform (a_mode 2) of the latent-0
+//    reverse chain, which is then ONE layer (4 steps instead of 6).
+//  * fold_embed_output: EDGE_EMBEDDING = a_e @ W1 (the linear output layer of scalar_embed_mlp, a_e = silu(h)) only ever enters
+//    linear maps -- env_embed_linear / first_layer_env_embed_projection (tensorembed.py:88-89, _allegro.py:251-258) and, through
+//    the moments, the env weights of layer 0.  With W1 folded into all of them (first stage: W1 @ [proj | env]; env weights:
+//    W1 @ Wenv0) the fused forward has no layer L1 either, works on a_e wherever it used the embedding and stores a_e in the
+//    embedding's slot; the reverse pass that FOLLOWS A FUSED FORWARD reads a_e there: tp_mom_bwd_first with the folded transposed
+//    env weights, and the last reverse chain is ONE 256 -> 64 layer ((W1 @ G0)^T, + d a_e of the moments, x silu'(h), contracted
+//    against the folded two-body table).  After a staged forward (true embedding stored) the unfolded reverse runs.
+// The single-layer pipeline's version of these folds for any depth is the "slot form" (aa_model_plan::slot_form, run-time switch
+// aa_plan_options.no_slot_form).
 constexpr int kFusedMaxDegree = 128;  // longest edge segment the fused forward takes: a team of four 32-edge tiles
 constexpr int kFusedTailAtomsPerCu = 64;   // from this many atoms per CU on the fused forward runs as eight-wave workgroups with the readout-reverse chain in its tail
 constexpr int kFusedTeamTilesSmall = 4096;  // up to this many tiles the team form is chosen regardless of how full the tiles are
@@ -737,58 +700,31 @@ struct FusedFwdArgs {
   float* fcat;     // [E,192] EDGE_FEATURES or nullptr
   float *x2s0, *x2s1;  // [N][D][64]
   float* atom_energy;  // [N]
-  int keep;            // split tile pairs held in registers by the one-tile w0-holding form: 0 none, 1 two-body scalars, 2 + lat0
+  int long_only;       // (host-only, set by launch_fused_fwd like skip_long / fill_done below; placed here so that the fields the
+                       //  kernels read keep their offsets -- the compiler's grouping of argument loads, and with it register
+                       //  allocation, follows them)
   int32_t* status;     // nullable, host-visible: set to the offending degree when a segment exceeds what the max_degree hint promised
   int mixed;           // with the class lists set: one-tile pass over all atoms (long ones skipped) + team pass over the long ones only
-  int skip_long, long_only, fill_done;  // (set by launch_fused_fwd for the two passes of the mixed form)
-  // two-waves-per-SIMD form with the readout-reverse chain in its tail (`tail` != 0; aa_fused8.hip): d EDGE_FEATURES[:, :128] and the
+  int skip_long, fill_done;  // (set by launch_fused_fwd for the two passes of the mixed form)
+  // two-waves-per-SIMD form with the readout-reverse chain in its tail (FusedForm::EightWaveTail; aa_fused8.hip): d EDGE_FEATURES[:, :128] and the
   // gradient of the layer-1 tensor-track scalars leave the forward kernel, the pre-activations of latent 1 / the readout do not
   float* g_fcat;
   float* g_scal1;
-  int ld_gfcat, tail;
-  int wide_one_per_cu; // two-waves-per-SIMD form, four-wave workgroups: ONE per CU (half the registers and LDS of a CU stay free for kernels of other streams)
-  int wide_proj_mfma;  // two-waves-per-SIMD form: env projections as bf16x3 layers on the matrix cores (its program then has 2 R steps per projection)
-  int wide_waves;      // two-waves-per-SIMD form (aa_fused8.hip): 4 = four-wave workgroups except on small boxes; -4 / -8: four / eight waves, forced
+  int ld_gfcat;
 };
 size_t fused_fwd_lds_bytes(int num_types, bool teams);  // dynamic LDS of the fused forward (aa_fused.hip); the CU has 160 KB
-// reverse tail (aa_fused_bwd.hip): layer-0 tensor product reverse + first-stage / scalar_embed_mlp reverse + edge reverse
-struct FusedTailArgs {
-  int64_t N, atom0, atom_end;  // atoms [atom0, atom_end), one wave each; every one has <= 32 edges
-  const int32_t *rowptr, *nbr, *types;
-  int num_types, embed_kind, spline_span;
-  float poly_p;
-  const float *rmax_recip, *bessel_w;
-  const float* emb_tab;      // [T*T][8][64]
-  const void* wstep[kFusedMaxSteps][2];  // weight program, 12-KB blocks (see fused_bwd_tail_kernel)
-  const float *tpw0, *tpw1;  // path weights
-  int coupling;
-  float sf;                  // 1/sqrt(avg_num_neighbors)
-  // inputs
-  const float* vec;          // [E,4] unit vector, length (forward)
-  const float* w0;           // [E,R*64] (forward)
-  const float* emb;          // [E,64] EDGE_EMBEDDING (forward)
-  const float* se_h;         // [E,64] pre-activation of scalar_embed_mlp's hidden layer (forward)
-  const float *x2s0, *x2s1;  // [N][D][64] (forward)
-  const float *gscal0, *gscal1;  // [E,64] gradients of the tensor-track scalars of the two layers
-  const float* g_tb;         // [E, ld_gtb] gradient of the two-body scalars (first 64 columns of d EDGE_FEATURES)
-  int ld_gtb;
-  const float* gsh_env1;     // [E,D] dE/dY of the layer-1 env path (tp_mom_bwd_last) or nullptr
-  // outputs: dvec [E,4] = dE/dr_e (edge reverse fused), or -- dvec == nullptr -- the inputs of edge_backward
-  float* dvec;
-  float* trev;               // [E,8]
-  float* gsh_out;            // [E,D]
-};
-int fused_bwd_tail_num_steps(int R);
-int fused_bwd_tail_chunk_order(int R, int i);
-int launch_fused_bwd_tail(int pair, const FusedTailArgs& a, hipStream_t stream);
-int fused_fwd_num_steps(int R, bool hold_w0);
-// `wide` (nullable): the same arguments with the weight program of the eight-wave form (aa_fused8.hip) -- it then takes the one-tile
+// Form of the one-tile pass of the fused forward (decided once per step by Runner::forward_fused): the one-wave-per-SIMD kernel
+// (aa_fused.hip), or the two-waves-per-SIMD kernel (aa_fused8.hip) as two four-wave workgroups per CU, one eight-wave workgroup per
+// CU, or eight waves with the readout-reverse chain in its tail.  A team pass over the long atoms (mixed form) always runs one wave
+// per SIMD.
+enum class FusedForm { OneWave, FourWave, EightWave, EightWaveTail };
+int fused_fwd_num_steps(int R);
+// `wide` (the same arguments with the weight program of the two-waves-per-SIMD form; set unless `form` is OneWave) takes the one-tile
 // pass (all atoms, or all but the long ones of the mixed form); the team pass keeps `a`
-int launch_fused_fwd(int pair, bool hold_w0, const FusedFwdArgs& a, hipStream_t stream, const FusedFwdArgs* wide = nullptr, bool* ran_wide = nullptr);
-int fused_fwd8_num_steps(int R, bool proj_mfma, bool tail = false);
-int fused_num_cus();  // CUs of the current device (the small-box rule of launch_fused_fwd)
+int launch_fused_fwd(int pair, FusedForm form, const FusedFwdArgs& a, const FusedFwdArgs* wide, hipStream_t stream);
+int fused_fwd8_num_steps(int R, bool tail);
 size_t fused_fwd8_lds_bytes(int num_types, int waves);  // per workgroup of 8 waves (one per CU) or 4 waves (two per CU)
-int launch_fused_fwd8(int pair, int waves, const FusedFwdArgs& a, hipStream_t stream);
+int launch_fused_fwd8(int pair, FusedForm form, const FusedFwdArgs& a, hipStream_t stream);  // form: FourWave, EightWave or EightWaveTail
 
 
 // ----------------------------------------------------------------------------------------------

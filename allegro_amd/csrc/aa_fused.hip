@@ -21,9 +21,8 @@
 // B[a][ch]) live in the transposed view lane = k / channel; the two views exchange through a wave-private LDS patch:
 //   moments   M[j][k] = sum_e Y[e][j] a[e][k]      tile -> LDS [e][k] -> lane k walks the 32 rows
 //   scalars   scal[e][ch] = sum_r w0[e][r][ch] * (sum_{a in r} Y[e][a] B[a][ch])      B from LDS (broadcast reads),
-//             evaluated in the epilogue of the GEMM tile pair that produces w0[.][r][.] -- w0 is never stored for
-//             the forward's own use and is recomputed (6 MFMA steps) for the second layer instead of being held in
-//             96 registers or re-read from HBM.
+//             evaluated in the epilogue of the GEMM tile pair that produces w0[.][r][.] -- w0 is held in registers
+//             (2 R tiles) for the second layer, never re-read from HBM or recomputed.
 // Weights stream L2 -> LDS once per workgroup (4 waves = 4 atoms share every 12-KB step, double buffered), exactly
 // the staging of gemm_chain_bf16x3_kernel.
 //
@@ -56,10 +55,7 @@ __device__ unsigned long long g_fused_ticks[32];
 
 // number of weight-pipeline steps of the program for R irreps: what the host builds (aa_model.hip: forward_fused) and what the
 // kernel consumes -- asserted against each other at compile time (a silent mismatch shifts every later layer's weights)
-constexpr int fused_fwd_steps(int R, bool hold) {
-  const int ps = kProjMfma ? 2 * R : 4;  // one env projection
-  return (kFoldEmbed ? (kFoldEmb1 ? 0 : 2) : 4) + ps + (2 + 2 * R) + 4 + ps + (kFoldLatent ? 0 : 2) + (hold ? 0 : 2 * R) + 6 + (kFoldLatent ? 0 : 2) + 6;
-}
+constexpr int fused_fwd_steps(int R) { return 4 + (2 + 2 * R) + 4 + 4 + 6 + 6; }
 
 // x[D] (lane = channel) summed over the waves [first, first + tsize) of a team, in that order (every member ends up with the
 // same bits); tsize is workgroup-uniform, so the barrier is too.  The exchange area is reused by the next call only after
@@ -91,19 +87,18 @@ constexpr int kTeamFloats = 4 * 16 * 64 + 4;
 
 // KEEP: tile pairs that feed several later layers and are therefore split into their bf16 levels ONCE, where they are produced,
 // and held in registers as MFMA operands (48 registers per pair) instead of being parked raw in LDS and split again by every
-// layer that reads them: 0 none (LDS parking), 1 the two-body scalars (read by L3, L6, L8), 2 also lat0 (L6, L8).  The
-// one-tile, w0-holding instantiation has the registers to spare (366 of 512 before).
-template <class Sig0, class Sig1, bool HOLD, bool TEAMS, int KEEP = 0>
+// layer that reads them: 0 none (LDS parking), 1 the two-body scalars (read by L3, L6, L8), 2 also a1 of latent 0 (L6, L8).
+// The one-tile form has the registers to spare; the team form parks.
+template <class Sig0, class Sig1, bool TEAMS>
 __global__ __launch_bounds__(256, kFusedOcc) void fused_fwd_kernel(FusedFwdArgs A) {
   constexpr int D = Sig0::D2, R = Sig0::LMAX + 1;
+  constexpr int KEEP = TEAMS ? 0 : kFusedKeepDefault;
   static_assert(Sig0::D1 == D && Sig0::DOUT == D && Sig1::D1 == D && Sig1::DOUT == 1, "standard 2-layer stack");
   static_assert(D <= 16, "l_max <= 3");
-  // the program: L0 L1 | Wenv0 | L2 | L3 | Wenv1 | L4 | (L5: w0 again, unless held) | L6 L7 L8
-  constexpr int kPS = kProjMfma ? 2 * R : 4;  // pipeline steps of one env projection
-  constexpr int S_L0 = 0, S_L1 = kFoldEmbed ? 0 : 2, S_P0 = S_L1 + (kFoldEmb1 ? 0 : 2), S_L2 = S_P0 + kPS, S_L3 = S_L2 + 2 + 2 * R, S_P1 = S_L3 + 4, S_L4 = S_P1 + kPS,
-                S_L5 = S_L4 + (kFoldLatent ? 0 : 2), S_L6 = S_L5 + (HOLD ? 0 : 2 * R), S_L7 = S_L6 + 6, S_L8 = S_L7 + (kFoldLatent ? 0 : 2), NS = S_L8 + 6;
+  // the program (folded, see aa_common.h; L0 L1 L4 L7 are folded away and w0 is held for L5): Wenv0 | L2 | L3 | Wenv1 | L6 | L8
+  constexpr int S_P0 = 0, S_L2 = S_P0 + 4, S_L3 = S_L2 + 2 + 2 * R, S_P1 = S_L3 + 4, S_L6 = S_P1 + 4, S_L8 = S_L6 + 6, NS = S_L8 + 6;
   static_assert(NS % 2 == 0 && NS <= kFusedMaxSteps, "the two LDS buffers alternate consistently across iterations");
-  static_assert(NS == fused_fwd_steps(R, HOLD), "kernel and host disagree about the length of the weight program");
+  static_assert(NS == fused_fwd_steps(R), "kernel and host disagree about the length of the weight program");
   u32x4* wbuf = reinterpret_cast<u32x4*>(aa_smem);
   float* sRo = reinterpret_cast<float*>(wbuf + 2 * kWStep);            // [64] last readout weights
   float* sRm = sRo + 64;                                               // [16: T*T <= 9 used] 1 / r_max per type pair, then [8] Bessel roots at 16
@@ -312,54 +307,29 @@ __global__ __launch_bounds__(256, kFusedOcc) void fused_fwd_kernel(FusedFwdArgs 
       }
     }
     v16f k0, k1, sc0, sc1;
-    v16f w0t[HOLD ? 2 * R : 1];
+    v16f w0t[2 * R];
     XSplit tb[KEEP >= 1 ? 2 : 1], l0x[KEEP >= 2 ? 2 : 1];  // held split tiles (see KEEP)
     AA_TICK(2)
-    // ---- L0: scalar_embed_mlp layer 0 (pre-activation kept for the reverse pass).  Folded into the table (kFoldEmbed): em0 / em1
-    //      ARE its pre-activation, no GEMM
-    if constexpr (kFoldEmbed) {
-      tile_store_rows(sW, em0, A.se_h, row0, cnt, 64, lane);
-      tile_store_rows(sW, em1, A.se_h + 32, row0, cnt, 64, lane);
-      keep_tile<true>(em0, k0);
-      keep_tile<true>(em1, k1);
-    } else {
-      fused_layer<S_L0, NS, 2, 2>(A, p,
-                                  [&](auto kc) -> const v16f& { if constexpr (decltype(kc)::value == 0) return em0; else return em1; },
-                                  [&](auto, const v16f& a0, const v16f& a1) {
-                                    tile_store_rows(sW, a0, A.se_h, row0, cnt, 64, lane);
-                                    tile_store_rows(sW, a1, A.se_h + 32, row0, cnt, 64, lane);
-                                    keep_tile<true>(a0, k0);
-                                    keep_tile<true>(a1, k1);
-                                  });
-    }
+    // ---- L0: scalar_embed_mlp layer 0 (pre-activation kept for the reverse pass).  Folded into the table (fold_embed_table):
+    //      em0 / em1 ARE its pre-activation, no GEMM
+    tile_store_rows(sW, em0, A.se_h, row0, cnt, 64, lane);
+    tile_store_rows(sW, em1, A.se_h + 32, row0, cnt, 64, lane);
+    keep_tile<true>(em0, k0);
+    keep_tile<true>(em1, k1);
     AA_TICK(3)
-    // ---- L1: scalar_embed_mlp layer 1 -> EDGE_EMBEDDING.  Folded (kFoldEmb1): every consumer of the embedding is linear, so they
-    //      take a_e = silu(h) (k0, k1) against W1-folded weights; a_e is stored in the embedding's slot for the reverse pass
-    if constexpr (kFoldEmb1) {
-      em0 = k0;
-      em1 = k1;
-      tile_store_rows(sW, em0, A.emb, row0, cnt, 64, lane);
-      tile_store_rows(sW, em1, A.emb + 32, row0, cnt, 64, lane);
-    } else {
-      fused_layer<S_L1, NS, 2, 2>(A, p,
-                                  [&](auto kc) -> const v16f& { if constexpr (decltype(kc)::value == 0) return k0; else return k1; },
-                                  [&](auto, const v16f& a0, const v16f& a1) {
-                                    tile_store_rows(sW, a0, A.emb, row0, cnt, 64, lane);
-                                    tile_store_rows(sW, a1, A.emb + 32, row0, cnt, 64, lane);
-                                    em0 = a0;
-                                    em1 = a1;
-                                  });
-    }
+    // ---- L1: scalar_embed_mlp layer 1 -> EDGE_EMBEDDING.  Folded (fold_embed_output): every consumer of the embedding is linear,
+    //      so they take a_e = silu(h) (k0, k1) against W1-folded weights; a_e is stored in the embedding's slot for the reverse pass
+    em0 = k0;
+    em1 = k1;
+    tile_store_rows(sW, em0, A.emb, row0, cnt, 64, lane);
+    tile_store_rows(sW, em1, A.emb + 32, row0, cnt, 64, lane);
     AA_TICK(4)
     // ---- per-atom part of layer 0: moments of the embedding -> x2s0 -> B0 = Sig0^T_x1(e_0, x2s0)
     float x2s0[D];
     {
       float M[D];
       tile_moments<D>(sW, sY, em0, em1, lane, M);
-      if constexpr (kProjMfma)
-        project_moments_mfma<S_P0, NS, D, R>(A, p, sW, M, A.sf, x2s0);
-      else
-        project_moments<S_P0, NS, D, R>(A, p, sW, M, A.sf, x2s0);
+      project_moments<S_P0, NS, D, R>(A, p, sW, M, A.sf, x2s0);
       if constexpr (TEAMS) team_sum<D>(sTeam, wvs, tfirst, tsize, lane, x2s0);
       if (atom_ok && leader) {
 #pragma unroll
@@ -403,10 +373,8 @@ __global__ __launch_bounds__(256, kFusedOcc) void fused_fwd_kernel(FusedFwdArgs 
                                               tile_store_rows(sW, a1, A.w0 + (q - 1) * 64 + 32, row0, cnt, 64 * R, lane);
                                             }
                                             tile_scal_accumulate<q - 1>(sBv + 4 * hh, Y, a0, a1, sc0, sc1);
-                                            if constexpr (HOLD) {
-                                              w0t[2 * (q - 1)] = a0;
-                                              w0t[2 * (q - 1) + 1] = a1;
-                                            }
+                                            w0t[2 * (q - 1)] = a0;
+                                            w0t[2 * (q - 1) + 1] = a1;
                                           }
                                         });
     AA_TICK(6)
@@ -433,10 +401,7 @@ __global__ __launch_bounds__(256, kFusedOcc) void fused_fwd_kernel(FusedFwdArgs 
     {
       float M[D], x2s1[D];
       tile_moments<D>(sW, sY, k0, k1, lane, M);
-      if constexpr (kProjMfma)
-        project_moments_mfma<S_P1, NS, D, R>(A, p, sW, M, A.sf, x2s1);
-      else
-        project_moments<S_P1, NS, D, R>(A, p, sW, M, A.sf, x2s1);
+      project_moments<S_P1, NS, D, R>(A, p, sW, M, A.sf, x2s1);
       if constexpr (TEAMS) team_sum<D>(sTeam, wvs, tfirst, tsize, lane, x2s1);
       if (atom_ok && leader) {
 #pragma unroll
@@ -450,53 +415,27 @@ __global__ __launch_bounds__(256, kFusedOcc) void fused_fwd_kernel(FusedFwdArgs 
       __builtin_amdgcn_wave_barrier();
     }
     AA_TICK(8)
-    // ---- L4: latent 0, output layer -> lat0.  Folded (kFoldLatent): lat0 is never formed -- its consumers L6 / L8 take the hidden
-    //      activation a1 = silu(h) (k0, k1) against Wout_0 @ their lat0 row blocks; a1 is what is held / parked instead
-    if constexpr (kFoldLatent) {
-      if constexpr (KEEP >= 2) {
-        xsplit_from_acc(k0, l0x[0]);
-        xsplit_from_acc(k1, l0x[1]);
-      } else {
-        AA_PARK(2, k0);
-        AA_PARK(3, k1);
-      }
+    // ---- L4: latent 0, output layer -> lat0.  Folded (fold_latent_outputs): lat0 is never formed -- its consumers L6 / L8 take the
+    //      hidden activation a1 = silu(h) (k0, k1) against Wout_0 @ their lat0 row blocks; a1 is what is held / parked instead
+    if constexpr (KEEP >= 2) {
+      xsplit_from_acc(k0, l0x[0]);
+      xsplit_from_acc(k1, l0x[1]);
     } else {
-      fused_layer<S_L4, NS, 2, 2>(A, p,
-                                  [&](auto kc) -> const v16f& { if constexpr (decltype(kc)::value == 0) return k0; else return k1; },
-                                  [&](auto, const v16f& a0, const v16f& a1) {
-                                    if constexpr (KEEP >= 2) {
-                                      xsplit_from_acc(a0, l0x[0]);
-                                      xsplit_from_acc(a1, l0x[1]);
-                                    } else {
-                                      AA_PARK(2, a0);
-                                      AA_PARK(3, a1);
-                                    }
-                                    if (A.fcat) {
-                                      tile_store_rows(sW, a0, A.fcat + 64, row0, cnt, 192, lane);
-                                      tile_store_rows(sW, a1, A.fcat + 96, row0, cnt, 192, lane);
-                                    }
-                                  });
+      AA_PARK(2, k0);
+      AA_PARK(3, k1);
     }
     // inputs of the next tile (its neighbor ids arrived long ago): positions, shifts, types
     load_geo(a_nxt, nxt);
     AA_TICK(9)
-    // ---- L5: layer-1 scalars with B1 -- from the held w0 tiles, or from w0 recomputed out of the embedding
+    // ---- L5: layer-1 scalars with B1 from the held w0 tiles
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       sc0[r] = 0.f;
       sc1[r] = 0.f;
     }
-    if constexpr (HOLD) {
-      static_for<0, R>([&](auto rr) {
-        tile_scal_accumulate<decltype(rr)::value>(sBv + 4 * hh, Y, w0t[2 * decltype(rr)::value], w0t[2 * decltype(rr)::value + 1], sc0, sc1);
-      });
-    } else {
-      fused_layer<S_L5, NS, 2, 2 * R>(A, p,
-                                      [&](auto kc) -> const v16f& { if constexpr (decltype(kc)::value == 0) return em0; else return em1; },
-                                      [&](auto ntp, const v16f& a0, const v16f& a1) {
-                                        tile_scal_accumulate<decltype(ntp)::value>(sBv + 4 * hh, Y, a0, a1, sc0, sc1);
-                                      });
-    }
+    static_for<0, R>([&](auto rr) {
+      tile_scal_accumulate<decltype(rr)::value>(sBv + 4 * hh, Y, w0t[2 * decltype(rr)::value], w0t[2 * decltype(rr)::value + 1], sc0, sc1);
+    });
     AA_TICK(10)
     // ---- L6: latent 1, hidden layer: [two-body | lat0 | scal1]
     fused_layer<S_L6, NS, 6, 2>(A, p,
@@ -519,19 +458,7 @@ __global__ __launch_bounds__(256, kFusedOcc) void fused_fwd_kernel(FusedFwdArgs 
                                   keep_tile<true>(a1, k1);
                                 });
     AA_TICK(11)
-    // ---- L7: latent 1, output layer -> lat1.  Folded (kFoldLatent): the readout takes silu(h) of latent 1 (k0, k1) directly
-    if constexpr (!kFoldLatent) {
-      fused_layer<S_L7, NS, 2, 2>(A, p,
-                                  [&](auto kc) -> const v16f& { if constexpr (decltype(kc)::value == 0) return k0; else return k1; },
-                                  [&](auto, const v16f& a0, const v16f& a1) {
-                                    k0 = a0;
-                                    k1 = a1;
-                                    if (A.fcat) {
-                                      tile_store_rows(sW, a0, A.fcat + 128, row0, cnt, 192, lane);
-                                      tile_store_rows(sW, a1, A.fcat + 160, row0, cnt, 192, lane);
-                                    }
-                                  });
-    }
+    // ---- L7: latent 1, output layer -> lat1.  Folded (fold_latent_outputs): the readout takes silu(h) of latent 1 (k0, k1) directly
     AA_TICK(12)
     // ---- L8: edge readout hidden layer on [two-body | lat0 | lat1]; last linear layer + edge sum in the epilogue
     fused_layer<S_L8, NS, 6, 2>(A, p,
@@ -618,114 +545,79 @@ size_t fused_fwd_lds_bytes(int num_types, bool teams) {
 }
 
 // number of weight-pipeline steps of the program for R irreps (see the kernel)
-int fused_fwd_num_steps(int R, bool hold) { return fused_fwd_steps(R, hold); }
+int fused_fwd_num_steps(int R) { return fused_fwd_steps(R); }
 
-static int launch_fused_fwd_one(int pair, bool hold_w0, const FusedFwdArgs& a, hipStream_t stream);
+static int launch_fused_fwd_one(int pair, const FusedFwdArgs& a, hipStream_t stream);
+
+// E_i = shift_t for the atoms outside the block, once per step (not by the team pass of the mixed form: fill_done)
+static void fill_outside_energy(const FusedFwdArgs& a, hipStream_t stream) {
+  if (a.N > 0 && (a.atom0 > 0 || a.atom_end < a.N) && !a.fill_done) {
+    hipLaunchKernelGGL(fused_fill_energy_kernel, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, stream, a.N, a.atom0, a.atom_end,
+                       a.types, a.shifts, a.atom_energy);
+  }
+}
 
 // Mixed form (a.mixed, with the class lists set): most atoms have one tile of edges, a FEW have more (thermal disorder pushes a
 // handful of Si atoms past 32 neighbours; profiles/r05_v23_md_loop_c4.json).  The team form costs every atom ~12 % (class lists,
 // exchange area, 2 fewer tile parkings), the staged pipeline ~12 % of the step: instead the one-tile kernel runs over all atoms at
 // full speed and SKIPS the long ones, and a second, small launch of the team form takes exactly those (its grid is the list).
-int fused_num_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-  }
-  return cus;
-}
-
-int launch_fused_fwd(int pair, bool hold_w0, const FusedFwdArgs& a, hipStream_t stream, const FusedFwdArgs* wide, bool* ran_wide) {
-  if (ran_wide) *ran_wide = false;
+// The one-tile pass runs in `form` (decided by the caller, Runner::forward_fused); team passes always run on the one-wave kernel.
+int launch_fused_fwd(int pair, FusedForm form, const FusedFwdArgs& a, const FusedFwdArgs* wide, hipStream_t stream) {
   const bool teams = a.tile_atoms != nullptr;
-  // (boxes that leave a CU at most one workgroup run one wave per SIMD whatever the kernel: there the register-rich one-tile form --
-  //  w0 held, operands kept split -- is the faster one: 64 atoms 44 vs 48 us, profiles/r06_v4_ab_c2_*)
-  if (wide && wide->wide_waves > 0 && a.atom_end - a.atom0 <= int64_t(4) * fused_num_cus()) wide = nullptr;
-  if (wide && (!teams || a.mixed)) {
-    // the one-tile pass on the eight-wave form (two waves per SIMD); the team pass over the long atoms, if any, as below
-    if (a.atom_end <= a.atom0) return AA_OK;
-    if (a.N > 0 && (a.atom0 > 0 || a.atom_end < a.N) && !a.fill_done) {
-      hipLaunchKernelGGL(fused_fill_energy_kernel, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, stream, a.N, a.atom0, a.atom_end,
-                         a.types, a.shifts, a.atom_energy);
-    }
-    FusedFwdArgs one = *wide;
-    one.tile_atoms = nullptr;
-    one.tile_counts = nullptr;
-    one.tile_cap = 0;
-    one.skip_long = teams ? 1 : 0;
-    if (int rc = launch_fused_fwd8(pair, wide->wide_waves == -8 ? 8 : 4, one, stream)) return rc;
-    if (ran_wide) *ran_wide = true;
-    if (!teams) return AA_OK;
-    FusedFwdArgs team = a;
-    team.long_only = 1;
-    team.fill_done = 1;
-    return launch_fused_fwd_one(pair, hold_w0, team, stream);
-  }
-  if (!a.mixed || a.tile_atoms == nullptr) return launch_fused_fwd_one(pair, hold_w0, a, stream);
-  FusedFwdArgs one = a;
+  if (form == FusedForm::OneWave && (!teams || !a.mixed)) return launch_fused_fwd_one(pair, a, stream);  // one-tile or pure team form
+  if (form != FusedForm::OneWave && (!wide || (teams && !a.mixed))) return fail(AA_ERR_INVALID, "fused forward: the two-waves-per-SIMD form takes the one-tile pass only");
+  // the one-tile pass (mixed form: over all atoms, the long ones skipped), then the team pass over the long ones
+  FusedFwdArgs one = form == FusedForm::OneWave ? a : *wide;
   one.tile_atoms = nullptr;
   one.tile_counts = nullptr;
   one.tile_cap = 0;
-  one.skip_long = 1;
-  if (int rc = launch_fused_fwd_one(pair, hold_w0, one, stream)) return rc;
+  one.skip_long = teams ? 1 : 0;
+  if (form == FusedForm::OneWave) {
+    if (int rc = launch_fused_fwd_one(pair, one, stream)) return rc;
+  } else if (a.atom_end > a.atom0) {
+    fill_outside_energy(one, stream);
+    if (int rc = launch_fused_fwd8(pair, form, one, stream)) return rc;
+  }
+  if (!teams) return AA_OK;
   FusedFwdArgs team = a;
   team.long_only = 1;
   team.fill_done = 1;
-  return launch_fused_fwd_one(pair, hold_w0, team, stream);
+  return launch_fused_fwd_one(pair, team, stream);
 }
 
-static int launch_fused_fwd_one(int pair, bool hold_w0, const FusedFwdArgs& a, hipStream_t stream) {
+static int launch_fused_fwd_one(int pair, const FusedFwdArgs& a, hipStream_t stream) {
   if (a.atom_end <= a.atom0) return AA_OK;
   const bool teams = a.tile_atoms != nullptr;
   const size_t smem = fused_fwd_lds_bytes(a.num_types, teams);
   if (smem > 160 * 1024) return fail(AA_ERR_INVALID, "fused forward: LDS budget exceeded");
-  if (a.N > 0 && (a.atom0 > 0 || a.atom_end < a.N) && !a.fill_done) {
-    hipLaunchKernelGGL(fused_fill_energy_kernel, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, stream, a.N, a.atom0, a.atom_end,
-                       a.types, a.shifts, a.atom_energy);
-  }
+  fill_outside_energy(a, stream);
   // persistent: one workgroup per CU (the kernel needs the whole register file and most of the LDS of a CU)
-  static int num_cu = 0;
-  if (num_cu == 0) {
-    int dev = 0, n = 0;
-    AA_CHECK_HIP(hipGetDevice(&dev));
-    AA_CHECK_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-    num_cu = n > 0 ? n : 256;
-  }
+  const int cus = device_cu_count();
+  if (cus < 0) return cus;
   // TEAMS: the number of groups is only known on the device (class counters): at most one group per atom
   const int64_t ngroups = teams ? a.atom_end - a.atom0 : (a.atom_end - a.atom0 + 3) / 4;
-  dim3 grid((unsigned)std::min<int64_t>(ngroups, int64_t(num_cu) * kFusedOcc));
+  dim3 grid((unsigned)std::min<int64_t>(ngroups, int64_t(cus) * kFusedOcc));
   if (teams) {
     AA_CHECK_HIP(hipMemsetAsync(a.tile_counts, 0, 4 * sizeof(int32_t), stream));
     hipLaunchKernelGGL(fused_classify_kernel, dim3((unsigned)((a.atom_end - a.atom0 + 255) / 256)), dim3(256), 0, stream, a.atom0, a.atom_end,
                        a.rowptr, a.tile_cap, a.tile_atoms, a.tile_counts, a.long_only ? 32 : -1);
   }
-#define AA_FUSED_LAUNCH1(S0_, S1_, H_, T_)                                                                     \
-  {                                                                                                            \
-    const void* fn = (const void*)fused_fwd_kernel<cg::S0_, cg::S1_, H_, T_>;                                  \
-    AA_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(smem)));              \
-    hipLaunchKernelGGL((fused_fwd_kernel<cg::S0_, cg::S1_, H_, T_>), grid, dim3(256), smem, stream, a);        \
+#define AA_FUSED_LAUNCH1(S0_, S1_, T_)                                                                     \
+  {                                                                                                        \
+    const void* fn = (const void*)fused_fwd_kernel<cg::S0_, cg::S1_, T_>;                                  \
+    AA_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(smem)));          \
+    hipLaunchKernelGGL((fused_fwd_kernel<cg::S0_, cg::S1_, T_>), grid, dim3(256), smem, stream, a);        \
   }
-#define AA_FUSED_LAUNCHK(S0_, S1_, K_)                                                                          \
-  {                                                                                                            \
-    const void* fn = (const void*)fused_fwd_kernel<cg::S0_, cg::S1_, true, false, K_>;                         \
-    AA_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(smem)));              \
-    hipLaunchKernelGGL((fused_fwd_kernel<cg::S0_, cg::S1_, true, false, K_>), grid, dim3(256), smem, stream, a); \
-  }
-  // (the one-tile, w0-holding form keeps split tile pairs in registers: a.keep, see the kernel's KEEP)
-#define AA_FUSED_LAUNCH(S0_, S1_, H_)                                                                            \
-  if (teams) AA_FUSED_LAUNCH1(S0_, S1_, H_, true)                                                                \
-  else if (H_ && a.keep == 1) AA_FUSED_LAUNCHK(S0_, S1_, 1)                                                      \
-  else if (H_ && a.keep == 2) AA_FUSED_LAUNCHK(S0_, S1_, 2)                                                      \
-  else AA_FUSED_LAUNCH1(S0_, S1_, H_, false)
+#define AA_FUSED_LAUNCH(S0_, S1_) \
+  if (teams) AA_FUSED_LAUNCH1(S0_, S1_, true) else AA_FUSED_LAUNCH1(S0_, S1_, false)
   if (pair == 0) {
-    if (hold_w0) AA_FUSED_LAUNCH(Sig1, Sig0, true) else AA_FUSED_LAUNCH(Sig1, Sig0, false)
+    AA_FUSED_LAUNCH(Sig1, Sig0)
   } else if (pair == 1) {
-    if (hold_w0) AA_FUSED_LAUNCH(Sig5, Sig4, true) else AA_FUSED_LAUNCH(Sig5, Sig4, false)
+    AA_FUSED_LAUNCH(Sig5, Sig4)
   } else {
     return fail(AA_ERR_INVALID, "fused forward: unsupported signature pair");
   }
 #undef AA_FUSED_LAUNCH
-#undef AA_FUSED_LAUNCHK
 #undef AA_FUSED_LAUNCH1
   AA_CHECK_HIP(hipGetLastError());
 #ifdef AA_FUSED_TIMING

@@ -13,7 +13,7 @@
 // step, so the 24 KB of double-buffered weight steps are shared by eight tiles (half the L2 -> LDS weight traffic and half the
 // staging work per tile).  Per wave 16.6 KB of LDS and <= 256 registers:
 //   * the two-body scalars (three consumers) are parked raw in LDS (8 KB), the latent-0 activation (two consumers) stays in 32
-//     registers; nothing is held pre-split (KEEP) and w0 is not held (HOLD): 192 registers of the one-tile form are gone;
+//     registers; nothing is held pre-split (KEEP) and w0 is not held in registers: 192 registers of the one-tile form are gone;
 //   * layer 1's tensor-track scalars take w0 from the rows this wave stored for the reverse pass a few thousand cycles earlier
 //     (L2-resident; 24 16-byte loads per lane) instead of recomputing it with 6 MFMA steps or holding it in 96 registers;
 //   * latent 1 and the readout hidden layer share their first four operand chunks [two-body | lat0]: the merged phase walks
@@ -187,7 +187,7 @@ struct TileIn8 {
 
 }  // namespace
 
-constexpr int fused_fwd8_steps(int R, bool pm, bool tail = false) { return (pm ? 2 * R : 4) + (2 + 2 * R) + 4 + (pm ? 2 * R : 4) + 2 + 8 + 2 + (tail ? 12 : 0); }
+constexpr int fused_fwd8_steps(int R, bool tail) { return 4 + (2 + 2 * R) + 4 + 4 + 2 + 8 + 2 + (tail ? 12 : 0); }
 
 // WAVES = 8: one workgroup per CU, eight tiles in lock step (both two-body tiles parked in LDS: 16.6 KB per wave).
 // WAVES = 4: TWO independent workgroups per CU (78 KB of LDS each: one two-body tile parked, the other in 16 registers), each with
@@ -197,7 +197,7 @@ constexpr int fused_fwd8_steps(int R, bool pm, bool tail = false) { return (pm ?
 //       silu'(h1); d EDGE_FEATURES[:, :128] = [d ro_h | d h1] W_b; d scal1 = d h1 W_c -- 12 more steps on the same weight fragments the
 //       chain kernel uses) runs here, where its operands are in registers: the total energy is a plain sum, so the gradient seeds of
 //       every edge-local layer are known at the end of the edge's own forward.
-template <class Sig0, class Sig1, int WAVES, bool PM, bool TAIL = false>
+template <class Sig0, class Sig1, int WAVES, bool TAIL>
 __global__ __launch_bounds__(64 * WAVES, 2) void fused_fwd8_kernel(FusedFwdArgs A) {
   static_assert(WAVES == 8 || WAVES == 4, "workgroup forms");
   constexpr int NT = 64 * WAVES;                   // threads
@@ -206,11 +206,10 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fused_fwd8_kernel(FusedFwdArgs 
   constexpr int D = Sig0::D2, R = Sig0::LMAX + 1;
   static_assert(Sig0::D1 == D && Sig0::DOUT == D && Sig1::D1 == D && Sig1::DOUT == 1, "standard 2-layer stack");
   static_assert(D <= 9, "l_max <= 2");
-  static_assert(kFoldEmbed && kFoldEmb1 && kFoldLatent, "the wide form exists for the folded program only");
-  constexpr int kPS = PM ? 2 * R : 4;  // pipeline steps of one env projection
+  constexpr int kPS = 4;  // pipeline steps of one env projection
   constexpr int S_P0 = 0, S_L2 = kPS, S_L3 = S_L2 + 2 + 2 * R, S_P1 = S_L3 + 4, S_L6A = S_P1 + kPS, S_M = S_L6A + 2, S_L8K = S_M + 8, S_T = S_L8K + 2,
                 NS = S_T + (TAIL ? 12 : 0);
-  static_assert(NS % 2 == 0 && NS <= kFusedMaxSteps && NS == fused_fwd8_steps(R, PM, TAIL), "program length");
+  static_assert(NS % 2 == 0 && NS <= kFusedMaxSteps && NS == fused_fwd8_steps(R, TAIL), "program length");
   u32x4* wbuf = reinterpret_cast<u32x4*>(aa_smem);
   float* sRo = reinterpret_cast<float*>(wbuf + 2 * kWStep);  // [64] last readout weights
   float* sRm = sRo + 64;                                     // [16] 1 / r_max per type pair, [8] Bessel roots at 16
@@ -353,8 +352,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fused_fwd8_kernel(FusedFwdArgs 
       }
     }
     AA_TICK8(1)
-    // ---- two-body table: pre-activation h of scalar_embed_mlp's hidden layer (kFoldEmbed); a_e = silu(h) stands in for the
-    //      embedding (kFoldEmb1)
+    // ---- two-body table: pre-activation h of scalar_embed_mlp's hidden layer (fold_embed_table); a_e = silu(h) stands in for the
+    //      embedding (fold_embed_output)
     v16f em0, em1;
     {
       const float* tb = sTab + pair * 512 + 4 * hh;
@@ -397,10 +396,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fused_fwd8_kernel(FusedFwdArgs 
       for (int q = 0; q < Sig0::P; ++q) wp0[q] = load_pw(A.tpw0, Sig0::P, q);
       float M[D];
       tile_moments_half<D>(sW, sY, em0, em1, lane, M);
-      if constexpr (PM)
-        project_moments_mfma<S_P0, NS, D, R, kLdY8>(A, p, sW, M, A.sf, x2s0, sBv);
-      else
-        project_moments<S_P0, NS, D, R, kLdY8>(A, p, sW, M, A.sf, x2s0);
+      project_moments<S_P0, NS, D, R, kLdY8>(A, p, sW, M, A.sf, x2s0);
       if (atom_ok) {
 #pragma unroll
         for (int j = 0; j < D; ++j) *at_bytes(A.x2s0 + (atom * D + j) * 64, 4u * unsigned(lane)) = x2s0[j];
@@ -482,10 +478,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fused_fwd8_kernel(FusedFwdArgs 
       for (int q = 0; q < Sig1::P; ++q) wp1[q] = load_pw(A.tpw1, Sig1::P, q);
       float M[D], x2s1[D];
       tile_moments_half<D>(sW, sY, k0, k1, lane, M);
-      if constexpr (PM)
-        project_moments_mfma<S_P1, NS, D, R, kLdY8>(A, p, sW, M, A.sf, x2s1, sBv);
-      else
-        project_moments<S_P1, NS, D, R, kLdY8>(A, p, sW, M, A.sf, x2s1);
+      project_moments<S_P1, NS, D, R, kLdY8>(A, p, sW, M, A.sf, x2s1);
       if (atom_ok) {
 #pragma unroll
         for (int j = 0; j < D; ++j) *at_bytes(A.x2s1 + (atom * D + j) * 64, 4u * unsigned(lane)) = x2s1[j];
@@ -553,7 +546,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fused_fwd8_kernel(FusedFwdArgs 
       fused_step8<S_M + 6, NS>(A, p, xs[1], a60, a61, [&] {});
       fused_step8<S_M + 7, NS>(A, p, xs[1], a80, a81, [&] {});
       AA_TICK8(8)
-      // latent 1: pre-activation stored, a_1 = silu(h) feeds the readout (its output layer is folded: kFoldLatent)
+      // latent 1: pre-activation stored, a_1 = silu(h) feeds the readout (its output layer is folded: fold_latent_outputs)
       if constexpr (TAIL) {  // (the reverse of this layer runs below: its pre-activation is needed there, not in HBM)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -671,41 +664,31 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fused_fwd8_kernel(FusedFwdArgs 
 size_t fused_fwd8_lds_bytes(int num_types, int waves) {
   return sizeof(u32x4) * 2 * kWStep + sizeof(float) * (64 + 32 + size_t(num_types) * num_types * 512 + size_t(waves) * fused_wave_floats(waves));
 }
-int fused_fwd8_num_steps(int R, bool proj_mfma, bool tail) { return fused_fwd8_steps(R, proj_mfma, tail); }
+int fused_fwd8_num_steps(int R, bool tail) { return fused_fwd8_steps(R, tail); }
 
-int launch_fused_fwd8(int pair, int waves, const FusedFwdArgs& a, hipStream_t stream) {
+int launch_fused_fwd8(int pair, FusedForm form, const FusedFwdArgs& a, hipStream_t stream) {
   if (a.atom_end <= a.atom0) return AA_OK;
-  if (waves != 4 && waves != 8) return fail(AA_ERR_INVALID, "fused forward (wide): 4 or 8 waves per workgroup");
+  if (form == FusedForm::OneWave) return fail(AA_ERR_INVALID, "fused forward (wide): 4 or 8 waves per workgroup");
+  const int waves = form == FusedForm::FourWave ? 4 : 8;
+  const bool tail = form == FusedForm::EightWaveTail;
   const size_t smem = fused_fwd8_lds_bytes(a.num_types, waves);
   if (smem * (waves == 4 ? 2 : 1) > 160 * 1024) return fail(AA_ERR_INVALID, "fused forward (wide): LDS budget exceeded");
   if (!a.w0) return fail(AA_ERR_INVALID, "fused forward (wide): needs the w0 rows");
-  static int num_cu = 0;
-  if (num_cu == 0) {
-    int dev = 0, n = 0;
-    AA_CHECK_HIP(hipGetDevice(&dev));
-    AA_CHECK_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-    num_cu = n > 0 ? n : 256;
-  }
-  const int64_t ngroups = (a.atom_end - a.atom0 + waves - 1) / waves;
-  dim3 grid((unsigned)std::min<int64_t>(ngroups, int64_t(num_cu) * ((waves == 4 && !a.wide_one_per_cu) ? 2 : 1)));
   // (the tail exists for the eight-wave form: with four-wave workgroups -- 24 instead of 16 staging registers, one two-body tile in
   //  registers -- it spills 186 registers and the kernel takes 5.1-5.3 instead of 4.3 ms at C4, profiles/r06_v19_*)
-  if (a.tail && (waves != 8 || a.wide_proj_mfma || !a.g_fcat || !a.g_scal1)) return fail(AA_ERR_INVALID, "fused forward (wide): the reverse tail exists for the eight-wave form with vector projections");
-#define AA_FUSED8_LAUNCHT(S0_, S1_)                                                                                       \
-  {                                                                                                                        \
-    const void* fn = (const void*)fused_fwd8_kernel<cg::S0_, cg::S1_, 8, false, true>;                                     \
-    AA_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(smem)));                          \
-    hipLaunchKernelGGL((fused_fwd8_kernel<cg::S0_, cg::S1_, 8, false, true>), grid, dim3(512), smem, stream, a);           \
-  }
-#define AA_FUSED8_LAUNCH1(S0_, S1_, W_, P_)                                                                     \
+  if (tail && (!a.g_fcat || !a.g_scal1)) return fail(AA_ERR_INVALID, "fused forward (wide): the reverse tail needs its gradient outputs");
+  const int cus = device_cu_count();
+  if (cus < 0) return cus;
+  const int64_t ngroups = (a.atom_end - a.atom0 + waves - 1) / waves;
+  dim3 grid((unsigned)std::min<int64_t>(ngroups, int64_t(cus) * (waves == 4 ? 2 : 1)));
+#define AA_FUSED8_LAUNCH1(S0_, S1_, W_, T_)                                                                     \
   {                                                                                                           \
-    const void* fn = (const void*)fused_fwd8_kernel<cg::S0_, cg::S1_, W_, P_>;                                \
+    const void* fn = (const void*)fused_fwd8_kernel<cg::S0_, cg::S1_, W_, T_>;                                \
     AA_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(smem)));             \
-    hipLaunchKernelGGL((fused_fwd8_kernel<cg::S0_, cg::S1_, W_, P_>), grid, dim3(64 * W_), smem, stream, a);  \
+    hipLaunchKernelGGL((fused_fwd8_kernel<cg::S0_, cg::S1_, W_, T_>), grid, dim3(64 * W_), smem, stream, a);  \
   }
 #define AA_FUSED8_LAUNCH(S0_, S1_) \
-  if (a.tail) AA_FUSED8_LAUNCHT(S0_, S1_) else if (waves == 8 && a.wide_proj_mfma) AA_FUSED8_LAUNCH1(S0_, S1_, 8, true) else if (waves == 8) AA_FUSED8_LAUNCH1(S0_, S1_, 8, false) \
-  else if (a.wide_proj_mfma) AA_FUSED8_LAUNCH1(S0_, S1_, 4, true) else AA_FUSED8_LAUNCH1(S0_, S1_, 4, false)
+  if (tail) AA_FUSED8_LAUNCH1(S0_, S1_, 8, true) else if (waves == 8) AA_FUSED8_LAUNCH1(S0_, S1_, 8, false) else AA_FUSED8_LAUNCH1(S0_, S1_, 4, false)
   if (pair == 0) {
     AA_FUSED8_LAUNCH(Sig1, Sig0)
   } else if (pair == 1) {
@@ -714,7 +697,6 @@ int launch_fused_fwd8(int pair, int waves, const FusedFwdArgs& a, hipStream_t st
     return fail(AA_ERR_INVALID, "fused forward (wide): unsupported signature pair");
   }
 #undef AA_FUSED8_LAUNCH1
-#undef AA_FUSED8_LAUNCHT
 #undef AA_FUSED8_LAUNCH
   AA_CHECK_HIP(hipGetLastError());
 #ifdef AA_FUSED_TIMING

@@ -3,6 +3,7 @@
 // w.r.t. positions (what ForceStressOutput's autograd does, allegro_models.py:101-103).
 // All kernels are enqueued on the caller's stream; all tensors live in caller-owned HBM buffers.
 #include <algorithm>
+#include <atomic>
 
 #include "aa_common.h"
 
@@ -12,6 +13,18 @@ void set_error(const std::string& msg) { g_err = msg; }
 int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
+}
+int device_cu_count() {
+  constexpr int kMaxDevices = 64;
+  static std::atomic<int> cached[kMaxDevices];  // per device id, 0 = not asked yet
+  int dev = 0, n = 0;
+  AA_CHECK_HIP(hipGetDevice(&dev));
+  const bool slot = dev >= 0 && dev < kMaxDevices;
+  if (slot && (n = cached[dev].load(std::memory_order_relaxed)) > 0) return n;
+  AA_CHECK_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+  if (n <= 0) return fail(AA_ERR_HIP, "hipDeviceGetAttribute: the device reports no compute units");
+  if (slot) cached[dev].store(n, std::memory_order_relaxed);
+  return n;
 }
 }  // namespace aa
 
@@ -222,22 +235,20 @@ struct aa_model_plan {
   int tp_op;                         // >= 0: signature chain of the per-atom operator kernels (aa_tp_op.hip; any L <= 3, u = 64 m)
   bool chain_gemm;                   // MLP chains fused into gemm_chain_bf16x3_kernel (hidden layers stay in registers)
   bool fused_fwd;                    // the whole forward as ONE per-atom-tile kernel when the graph allows (aa_fused.hip)
-  bool fused_hold_w0;                // ... holding the w0 tiles in registers between the two layers (else: recomputed)
   bool fused_wide = false;           // ... its one-tile pass on the eight-wave form (two waves per SIMD, aa_fused8.hip)
   mutable bool taps = false;         // aa_model_plan_enable_taps: staged pipeline so that every tap is materialised
   bool embed_fused;                  // reverse pass: d(two-body embedding) [E,S0] never materialised, the last reverse chain
                                      // contracts it back to the 8 basis functions in its epilogue (embrev_out in aa_common.h)
   size_t o_embtab;                   // [T*T][8][64] type_embed(c | pair) * basis_linear[n][c]
-  size_t o_embtab_h;                 // [T*T][8][64] the same table times the first scalar_embed_mlp layer (kFoldEmbed), or 0
-  size_t o_lat1in_fq, o_ro0_fq;      // (kFoldLatent, 2-layer 64-wide stacks) bf16x3 copies of the first layers of latent 1 / edge_readout with the
+  size_t o_embtab_h;                 // [T*T][8][64] the same table times the first scalar_embed_mlp layer (fold_embed_table), or 0
+  size_t o_lat1in_fq, o_ro0_fq;      // (fold_latent_outputs, 2-layer 64-wide stacks) bf16x3 copies of the first layers of latent 1 / edge_readout with the
                                      // latent output layers folded into their lat_l row blocks, or 0
   size_t o_b3af_q;                   // ... and of the merged first layer of the readout-reverse chain, or 0
   size_t o_b3bf_q;                   // ... and of its second layer with Wout_0^T folded into the lat0 columns (d a_0 instead of d lat0), or 0
-  size_t o_g0fq, o_g0tfq;            // (kFoldEmb1) bf16x3 copies of W1 @ G0 [64, ng0] and of its transpose, or 0
-  size_t o_wk0f, o_wt0f;             // (kFoldEmb1) W1 @ Wenv0 as [k][R][u] and [R][u][k], or 0
-  size_t o_wkq[AA_MAX_LAYERS];       // (kProjMfma, fused forward) Wenv_l as R bf16x3 64x64 layers [r][k -> ch] (layer 0: the folded one), or 0
+  size_t o_g0fq, o_g0tfq;            // (fold_embed_output) bf16x3 copies of W1 @ G0 [64, ng0] and of its transpose, or 0
+  size_t o_wk0f, o_wt0f;             // (fold_embed_output) W1 @ Wenv0 as [k][R][u] and [R][u][k], or 0
   // "Slot form" of the single-layer pipeline (operator-kernel plans: C5 and every standard stack off the tuned 2-layer shape).
-  // The same algebra as kFoldEmb1 / kFoldLatent, for any depth: the output layer of scalar_embed_mlp and of every latent MLP is
+  // The same algebra as fold_embed_output / fold_latent_outputs (aa_common.h), for any depth: the output layer of scalar_embed_mlp and of every latent MLP is
   // folded into its consumers at pack time, so slot l + 1 of the dense-net buffer holds the latent's hidden PRE-ACTIVATION z_l
   // (consumers activate those columns on load, GemmArgs::act_lo / act_hi) and the layers "a -> lat_l" do not exist.  The reverse
   // is evaluated BY SLOT, not by consumer: d z_l = ([d readout hidden | d z_{l+1} .. d z_{L-1}] @ stack_l + d a_l of the moments)
@@ -257,11 +268,6 @@ struct aa_model_plan {
   GemmMatSet s_pr[AA_MAX_LAYERS], s_prt[AA_MAX_LAYERS], s_pr0f, s_prt0f;
   int ng0;                           // output width of the fused first-stage GEMM
   size_t o_wk[AA_MAX_LAYERS], o_wt[AA_MAX_LAYERS];  // Wenv of layer l as [ka][R][u] and [R][u][ka]
-#ifdef AA_EXPERIMENTAL_TAIL
-  size_t o_wtk[AA_MAX_LAYERS];                      // ... and [u][R][ka] (the fused reverse tail streams it in 16-channel blocks)
-#endif
-  bool fused_tail;                   // (experimental build only) reverse: layer-0 tensor product reverse + first-stage /
-                                     // embed-MLP reverse + edge reverse as ONE per-atom-tile kernel (aa_fused_bwd.hip); measured slower than the staged tail
   size_t esize() const { return cfg.dtype == AA_F32 ? 4 : 8; }
   // optional hipGraph replay of the whole step (aa_model_plan_enable_graph): the launch sequence is captured once per
   // distinct argument set and replayed with one hipGraphLaunch -- for launch-bound (small) systems
@@ -419,7 +425,7 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
     const bool would_chain = cfg->dtype == AA_F32 && S == 64 && cfg->embed_mlp_depth == 1 && cfg->embed_mlp_width == 64 && cfg->latent_mlp_depth == 1 &&
                              cfg->latent_mlp_width == 64 && cfg->readout_mlp_depth == 1 && cfg->readout_mlp_width == 64 && cfg->embed_dim % 32 == 0 &&
                              !opt.gemm_no_chain && !opt.gemm_fp32_mfma && !opt.gemm_valu;
-    const bool would_slot = kSlotForm && !opt.no_slot_form && cfg->latent_mlp_depth == 1 && cfg->latent_mlp_width == S && cfg->readout_mlp_depth >= 1 &&
+    const bool would_slot = !opt.no_slot_form && cfg->latent_mlp_depth == 1 && cfg->latent_mlp_width == S && cfg->readout_mlp_depth >= 1 &&
                             cfg->embed_mlp_depth >= 1 && cfg->embed_mlp_width == S && (cfg->readout_mlp_width % 16) == 0;
     const bool prefer_op = p->env_mom && !would_chain && (would_slot || cfg->dtype == AA_F64) && !opt.tp_prefer_moments;
     if (all_silu && sigs_ok && L >= 2 && L <= 3 && (u % 64) == 0 && u <= 256 && (S == 64 || S == 128) && cfg->latent_mlp_depth >= 1 &&
@@ -478,9 +484,6 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
       const size_t ka = l == 0 ? S : cfg->latent_mlp_width;
       p->o_wk[l] = take(ka * p->W);
       p->o_wt[l] = take(ka * p->W);
-#ifdef AA_EXPERIMENTAL_TAIL
-      p->o_wtk[l] = take(ka * p->W);
-#endif
     }
   }
   for (int l = 0; l < L; ++l) {
@@ -497,20 +500,17 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
   p->o_b3a_q = p->o_b3b_q = p->o_b3c_q = 0;
   p->o_lat1in_fq = p->o_ro0_fq = p->o_b3af_q = p->o_b3bf_q = 0;
   p->o_g0fq = p->o_g0tfq = p->o_wk0f = p->o_wt0f = 0;
-  for (int l = 0; l < AA_MAX_LAYERS; ++l) p->o_wkq[l] = 0;
-  if (p->chain_gemm && p->env_mom && L == 2 && u == 64)  // (kProjMfma, and the two-waves-per-SIMD fused forward: env projection on the matrix cores)
-    for (int l = 0; l < L; ++l) p->o_wkq[l] = take(size_t(p->R) * gemm_bf16x3_words(64, 64));
-  if (kFoldEmb1 && p->chain_gemm && p->env_mom && L == 2 && u == 64) {
+  if (p->chain_gemm && p->env_mom && L == 2 && u == 64) {  // (fold_embed_output)
     p->o_g0fq = take(gemm_bf16x3_words(64, p->ng0));
     p->o_g0tfq = take(gemm_bf16x3_words(p->ng0, 64));
     p->o_wk0f = take(size_t(64) * p->W);
     p->o_wt0f = take(size_t(64) * p->W);
   }
-  if (kFoldLatent && p->chain_gemm && L == 2 && u == 64) {  // (chain_gemm: S = every MLP width = 64, one hidden layer each)
+  if (p->chain_gemm && L == 2 && u == 64) {  // (fold_latent_outputs; chain_gemm: S = every MLP width = 64, one hidden layer each)
     p->o_lat1in_fq = take(gemm_bf16x3_words(2 * S + u, 64));
     p->o_ro0_fq = take(gemm_bf16x3_words(3 * S, 64));
     p->o_b3af_q = take(gemm_bf16x3_words(64, 64));
-    if (kFoldLat0Rev) p->o_b3bf_q = take(gemm_bf16x3_words(128, S * L));
+    p->o_b3bf_q = take(gemm_bf16x3_words(128, S * L));  // (fold_lat0_reverse)
   }
   {
     // two-body table [T*T][B][S0] (type embedding x basis weights): the last reverse chain contracts against it (<= 2
@@ -520,7 +520,7 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
     p->embed_fused = tab_ok && T <= 2 && !opt.embed_no_fuse;
     p->o_embtab = (tab_ok || cfg->embed_kind == 1) ? take(size_t(T) * T * B * S0) : 0;
     // (the fold needs a hidden layer of 64 behind the embedding: what the chains / the fused forward require anyway)
-    p->o_embtab_h = (kFoldEmbed && tab_ok && cfg->embed_mlp_depth >= 1 && p->embed.dims.size() >= 2 && p->embed.dims[1] == 64) ? take(size_t(T) * T * B * 64) : 0;
+    p->o_embtab_h = (tab_ok && cfg->embed_mlp_depth >= 1 && p->embed.dims.size() >= 2 && p->embed.dims[1] == 64) ? take(size_t(T) * T * B * 64) : 0;
   }
   if (p->chain_gemm) {
     // merged reverse chain "readout' o latent_{L-1}'" (see Runner::backward): the readout-reverse columns that feed
@@ -531,7 +531,7 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
   }
   {
     const int De = cfg->embed_mlp_depth, Hr = cfg->readout_mlp_width, H = cfg->latent_mlp_width;
-    p->slot_form = kSlotForm && !opt.no_slot_form && !p->chain_gemm && p->tp_op >= 0 && p->env_mom && cfg->latent_mlp_depth == 1 && H == S &&
+    p->slot_form = !opt.no_slot_form && !p->chain_gemm && p->tp_op >= 0 && p->env_mom && cfg->latent_mlp_depth == 1 && H == S &&
                    cfg->readout_mlp_depth >= 1 && De >= 1 && cfg->embed_mlp_width == S && (Hr % 16) == 0;
     p->o_s_wk0 = p->o_s_wt0 = 0;
     if (p->slot_form) {
@@ -595,19 +595,11 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
     // aa_plan_options.fused_forward: 0 / 1 = whenever the graph allows (automatic), 3 = never (staged pipeline); A/B: 2 = also for every
     // graph with segments <= 128, in the pure team form, 4 = the same in the mixed form.
     const bool eligible = p->chain_gemm && p->env_mom && p->tp_op < 0 && (p->chain_pair == 0 || p->chain_pair == 1) && L == 2 &&
-                          u == 64 && S == 64 && T <= 3 && B == 8 && S0 == 64 && p->o_embtab != 0 && (!kFoldEmbed || p->o_embtab_h != 0) &&
-                          (!kFoldLatent || p->o_lat1in_fq != 0) && (!kFoldEmb1 || p->o_g0fq != 0) && (!kProjMfma || p->o_wkq[0] != 0);
+                          u == 64 && S == 64 && T <= 3 && B == 8 && S0 == 64 && p->o_embtab != 0 && p->o_embtab_h != 0 && p->o_lat1in_fq != 0 &&
+                          p->o_g0fq != 0;
     p->fused_fwd = eligible && opt.fused_forward != 3;
-#ifdef AA_EXPERIMENTAL_TAIL
-    p->fused_tail = p->fused_fwd && p->embed_fused && (opt.fused_tail == 1 || opt.fused_tail == 2);
-#else
-    p->fused_tail = false;
-#endif
-    p->fused_hold_w0 = !opt.fused_recompute_w0;  // A/B: recompute w0 for the second layer instead of holding it
-    // the eight-wave form needs the folded program (every fold active), a two-body table that leaves 16.6 KB of LDS per wave
-    // (one species) and the w0 rows of the staged reverse pass (no fused tail)
-    p->fused_wide = p->fused_fwd && kFoldEmbed && kFoldEmb1 && kFoldLatent && !kProjMfma && p->o_embtab_h != 0 && p->o_g0fq != 0 &&
-                    p->o_lat1in_fq != 0 && opt.fused_narrow != 1 && !p->fused_tail && fused_fwd8_lds_bytes(cfg->num_types, 8) <= 160 * 1024;
+    // the two-waves-per-SIMD form (aa_fused8.hip) needs a two-body table that leaves 16.6 KB of LDS per wave (one species)
+    p->fused_wide = p->fused_fwd && opt.fused_narrow != 1 && fused_fwd8_lds_bytes(cfg->num_types, 8) <= 160 * 1024;
   }
   {
     void* st = nullptr;
@@ -629,14 +621,14 @@ extern "C" int aa_model_plan_describe(const aa_model_plan* p, char* buf, size_t 
   // (after the folds) vs the step-equivalents of the reference's linear layers (what `roofline.achieved` prices)
   const int R = p->R;
   const int ref_steps = 2 + 2 + (2 + 2 * R) + 4 + 2 + 6 + 2 + 6;
-  const int exec_steps = fused ? fused_fwd_num_steps(R, p->fused_hold_w0) - 8 /* env-projection steps: vector work */ : 0;
+  const int exec_steps = fused ? fused_fwd_num_steps(R) - 8 /* env-projection steps: vector work */ : 0;
   const int k = snprintf(buf, n,
                          "{\"fused_forward\": %s, \"fold_embed_table\": %s, \"fold_embed_output\": %s, \"fold_latent_outputs\": %s, "
                          "\"fold_lat0_reverse\": %s, \"fused_mfma_steps_executed\": %d, \"fused_mfma_steps_reference\": %d, "
                          "\"chain_gemm\": %s, \"moments\": %s, \"operator_path\": %s, \"slot_form\": %s, \"fused_wide\": %s}",
-                         fused ? "true" : "false", (fused && kFoldEmbed && p->o_embtab_h) ? "true" : "false",
-                         (fused && kFoldEmb1 && p->o_g0fq) ? "true" : "false", (fused && kFoldLatent && p->o_lat1in_fq) ? "true" : "false",
-                         (kFoldLat0Rev && p->o_b3bf_q) ? "true" : "false", exec_steps, fused ? ref_steps : 0, p->chain_gemm ? "true" : "false",
+                         fused ? "true" : "false", (fused && p->o_embtab_h) ? "true" : "false",
+                         (fused && p->o_g0fq) ? "true" : "false", (fused && p->o_lat1in_fq) ? "true" : "false",
+                         p->o_b3bf_q ? "true" : "false", exec_steps, fused ? ref_steps : 0, p->chain_gemm ? "true" : "false",
                          p->env_mom ? "true" : "false", p->tp_op >= 0 ? "true" : "false", p->slot_form ? "true" : "false",
                          p->fused_wide ? "true" : "false");
   return (k < 0 || size_t(k) >= n) ? fail(AA_ERR_INVALID, "aa_model_plan_describe: buffer too small") : k;
@@ -728,15 +720,12 @@ extern "C" uint64_t aa_model_plan_layout_hash(const aa_model_plan* p) {
     mixs(p->s_pr0f); mixs(p->s_prt0f);
   }
   for (size_t v : {p->o_rmax, p->o_bessel, p->o_cemb, p->o_nemb, p->o_basis, p->o_g0, p->o_g0t, p->o_g0p, p->o_g0tp, p->o_g0q, p->o_g0tq,
-                   p->o_b3a_q, p->o_b3b_q, p->o_b3c_q, p->o_ro_last, p->o_scales, p->o_shifts, p->o_embtab, p->o_embtab_h, p->o_lat1in_fq, p->o_ro0_fq, p->o_b3af_q, p->o_b3bf_q, p->o_g0fq, p->o_g0tfq, p->o_wk0f, p->o_wt0f, p->o_wkq[0], p->o_wkq[1]})
+                   p->o_b3a_q, p->o_b3b_q, p->o_b3c_q, p->o_ro_last, p->o_scales, p->o_shifts, p->o_embtab, p->o_embtab_h, p->o_lat1in_fq, p->o_ro0_fq, p->o_b3af_q, p->o_b3bf_q, p->o_g0fq, p->o_g0tfq, p->o_wk0f, p->o_wt0f})
     mix(v);
   for (int l = 0; l < c.num_layers; ++l) {
     mix(p->o_tpw[l]);
     mix(p->env_mom ? p->o_wk[l] : 0);
     mix(p->env_mom ? p->o_wt[l] : 0);
-#ifdef AA_EXPERIMENTAL_TAIL
-    mix(p->env_mom ? p->o_wtk[l] : 0);
-#endif
     mixm(p->latent[l]);
   }
   mixm(p->embed);
@@ -932,9 +921,6 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
             double v = rawm[size_t(k) * raw_w + S + (shared ? ch : ch * Rr + r)] * al;
             h[p->o_wk[l] + (size_t(k) * Rr + r) * u + ch] = v;
             h[p->o_wt[l] + (size_t(r) * u + ch) * ka + k] = v;
-#ifdef AA_EXPERIMENTAL_TAIL
-            h[p->o_wtk[l] + (size_t(ch) * Rr + r) * ka + k] = v;
-#endif
           }
     };
     fill(0, raw->first_proj, S, S + We, mlp_alpha(c, 0, S, S + We - dWe));
@@ -967,7 +953,7 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
           }
   }
   if (p->o_wk0f) {
-    // (kFoldEmb1) env weights of layer 0 behind the output layer of scalar_embed_mlp: Wenv0'[k][r][ch] = sum_m W1[k][m] Wenv0[m][r][ch]
+    // (fold_embed_output) env weights of layer 0 behind the output layer of scalar_embed_mlp: Wenv0'[k][r][ch] = sum_m W1[k][m] Wenv0[m][r][ch]
     const double* w1 = &h[p->embed.w[1]];  // [64, S]
     const int Rr_ = p->R, uu = c.num_tensor;
     for (int k = 0; k < 64; ++k)
@@ -1142,19 +1128,8 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
       gemm_pack_bf16x3(b.data(), 128, SL, reinterpret_cast<unsigned*>(&hf[p->o_b3b_q]));
       gemm_pack_bf16x3(cmat.data(), 64, c.num_tensor, reinterpret_cast<unsigned*>(&hf[p->o_b3c_q]));
     }
-    for (int l = 0; l < L && l < 2; ++l) {
-      if (!p->o_wkq[l]) continue;
-      // (kProjMfma) env weights of layer l as one 64x64 bf16x3 layer per irrep: W_r[k][ch] = Wenv_l[k][r][ch]
-      const size_t src = (l == 0 && p->o_wk0f) ? p->o_wk0f : p->o_wk[l];
-      std::vector<float> wr(size_t(64) * 64);
-      for (int r = 0; r < p->R; ++r) {
-        for (int k = 0; k < 64; ++k)
-          for (int ch = 0; ch < 64; ++ch) wr[size_t(k) * 64 + ch] = float(h[src + (size_t(k) * p->R + r) * 64 + ch]);
-        gemm_pack_bf16x3(wr.data(), 64, 64, reinterpret_cast<unsigned*>(&hf[p->o_wkq[l] + size_t(r) * gemm_bf16x3_words(64, 64)]));
-      }
-    }
     if (p->o_g0fq) {
-      // (kFoldEmb1) first stage behind the output layer of scalar_embed_mlp: W1 @ G0 and its transpose
+      // (fold_embed_output) first stage behind the output layer of scalar_embed_mlp: W1 @ G0 and its transpose
       const int NG = p->ng0;
       std::vector<float> gf(size_t(64) * NG), gft(size_t(NG) * 64);
       for (int k = 0; k < 64; ++k)
@@ -1168,7 +1143,7 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
       gemm_pack_bf16x3(gft.data(), NG, 64, reinterpret_cast<unsigned*>(&hf[p->o_g0tfq]));
     }
     if (p->o_lat1in_fq) {
-      // folded first layers (kFoldLatent): row block "lat_l" of a consumer's first layer <- Wout_l @ that block, in fp64 from the
+      // folded first layers (fold_latent_outputs): row block "lat_l" of a consumer's first layer <- Wout_l @ that block, in fp64 from the
       // normalised matrices, rounded once.  Row order of the consumers: [two-body | lat0 | scal1] (latent 1), [two-body | lat0 | lat1] (readout)
       const double* wo0 = &h[p->latent[0].w[1]];  // [64, 64] output layer of latent 0
       const double* wo1 = &h[p->latent[1].w[1]];  // [64, 64] output layer of latent 1
@@ -1377,7 +1352,7 @@ struct Runner {
   StageProfile* prof = nullptr;
   bool want_forces = false;    // (set by run_model before forward())
   bool ro_grad_done = false;   // forward(): readout_reduce also wrote d E / d (last readout hidden layer) -- no readout_backward launch
-  bool fwd_b3_done = false;    // forward_fused(): the readout-reverse chain ran in the tail of the fused forward (FusedFwdArgs::tail)
+  bool fwd_b3_done = false;    // forward_fused(): the readout-reverse chain ran in the tail of the fused forward (FusedForm::EightWaveTail)
 
   // per_edge / per_atom: operand elements the launch must move (each distinct operand row once); see DESIGN.md §5
   int mark(const char* name, double per_edge = 0, double per_atom = 0, double flops = 0) {
@@ -1818,110 +1793,41 @@ struct Runner {
     if (fill >= 0.6 && fill <= 1.15) return true;
     return tiles <= kFusedTeamTilesSmall || double(g->num_edges) >= 0.85 * 32.0 * double(tiles);
   }
-  // the reverse tail in one launch (aa_fused_bwd.hip): same eligibility as the fused forward + the two-body table of the reverse
-  bool use_fused_tail(const aa_graph* g) const { return use_fused_fwd(g) && p->fused_tail; }
-  // the staged forward chains in the same folded form as the fused forward (kFoldEmb1, kFoldLatent): the hidden activations a_e /
+  // the staged forward chains in the same folded form as the fused forward (fold_embed_output, fold_latent_outputs): the hidden activations a_e /
   // a_0 are stored where the embedding / lat_0 used to be (ChainLayer::kept_out), consumers run on the folded matrices.  What
   // graphs with long segments -- dense systems, too large for the team form -- run.
   bool fold_staged() const {
-    return kFoldEmb1 && kFoldLatent && p->chain_gemm && p->tp_op < 0 && p->o_g0fq && p->o_lat1in_fq && p->o_wk0f && p->cfg.num_layers == 2 && !p->taps &&
+    return p->chain_gemm && p->tp_op < 0 && p->o_g0fq && p->o_lat1in_fq && p->o_wk0f && p->cfg.num_layers == 2 && !p->taps &&
            !p->opt.staged_no_fold;
   }
   // did the forward of this step leave a_e in the embedding's slot (folded first stage / env weights in the reverse)?
   bool folded_fwd(const aa_graph* g) const { return use_fused_fwd(g) || fold_staged(); }
-#ifdef AA_EXPERIMENTAL_TAIL
-  int backward_fused_tail(const aa_graph* g, void* forces) {
-    const aa_model_config& c = p->cfg;
-    const int u = c.num_tensor;
-    FusedTailArgs a{};
-    a.N = N;
-    a.atom0 = atom_begin(g);
-    a.atom_end = atom_end(g);
-    a.rowptr = g->rowptr;
-    a.nbr = g->nbr;
-    a.types = g->types;
-    a.num_types = c.num_types;
-    a.embed_kind = c.embed_kind;
-    a.spline_span = c.spline_span;
-    a.poly_p = float(c.poly_p);
-    auto wf = [&](size_t off) { return reinterpret_cast<const float*>(wt(off)); };
-    auto bf = [&](size_t off) { return reinterpret_cast<float*>(buf(off)); };
-    a.rmax_recip = wf(p->o_rmax);
-    a.bessel_w = wf(p->o_bessel);
-    a.emb_tab = wf(p->o_embtab);
-    int ns = 0;
-    {
-      const float* Wk = wf(p->o_wtk[0]);  // GM: 4 blocks of 16 channels x R x 64
-      for (int cblk = 0; cblk < 4; ++cblk) {
-        a.wstep[ns][0] = Wk + size_t(cblk) * 16 * p->R * 64;
-        a.wstep[ns][1] = Wk + size_t(cblk) * 16 * p->R * 64 + 1536;
-        ++ns;
-      }
-    }
-    auto add_layer = [&](const float* Wq, int KC, bool tail_order) {  // one tile pair (64 outputs), KC 32-deep chunks
-      for (int i = 0; i < KC; ++i) {
-        const int kc = tail_order ? fused_bwd_tail_chunk_order(p->R, i) : i;  // (the kernel consumes the w0 chunks half-major)
-        a.wstep[ns][0] = Wq + size_t(kc) * 64 * 24;
-        a.wstep[ns][1] = Wq + (size_t(KC) + kc) * 64 * 24;
-        ++ns;
-      }
-    };
-    add_layer(wf(p->o_g0tq), 2 + 2 * p->R, true);
-    add_layer(wf(p->embed.wtq[1]), 2, false);
-    add_layer(wf(p->embed.wtq[0]), 2, false);
-    if (ns != fused_bwd_tail_num_steps(p->R) || ns > kFusedMaxSteps) return fail(AA_ERR_INVALID, "fused reverse tail: program length mismatch");
-    a.tpw0 = wf(p->o_tpw[0]);
-    a.tpw1 = wf(p->o_tpw[1]);
-    a.coupling = c.tps[0].coupling;
-    a.sf = float(1.0 / std::sqrt(c.avg_num_neighbors));
-    a.vec = bf(w.vec);
-    a.w0 = bf(w.w0);
-    a.emb = bf(w.emb);
-    a.se_h = bf(w.se_h[0]);
-    a.x2s0 = bf(w.x2s[0]);
-    a.x2s1 = bf(w.x2s[1]);
-    a.gscal0 = bf(w.g_scal[0]);
-    a.gscal1 = bf(w.g_scal[1]);
-    a.g_tb = bf(w.g_fcat);
-    a.ld_gtb = p->SL1;
-    a.gsh_env1 = bf(w.g_sh) + size_t(2) * size_t(E) * p->D;  // slot of the layer-1 env path (tp_mom_bwd_last)
-    const bool gather = g->t_rowptr && g->t_perm;
-    const bool fuse_edge = gather && p->opt.fused_tail != 2;
-    if (fuse_edge) {
-      a.dvec = bf(w.dvec);
-    } else {
-      a.trev = bf(w.trev);
-      a.gsh_out = bf(w.g_sh);  // slot 0 carries the complete dE/dY
-    }
-    if (int rc = launch_fused_bwd_tail(p->chain_pair, a, stream)) return rc;
-    // algorithmic traffic per edge: neighbor id, unit vector, w0, embedding, one pre-activation, three gradient rows, the
-    // layer-1 dE/dY slot in; dE/dr_e (or the 8 basis sums + dE/dY) out.  Per atom: two x2s blocks, row pointer.
-    const double per_edge = 1 + 4 + p->W + 64 + 64 + 2.0 * u + 64 + p->D + (fuse_edge ? 4 : 8 + p->D);
-    const double fl = 2.0 * double(E) * (double(p->ng0) * 64 + 64.0 * 64 + 64.0 * c.embed_dim);
-    if (int rc = mark("fused_bwd_tail", per_edge, 2.0 * p->D * u + 1, fl)) return rc;
-    if (!fuse_edge) {
-      EdgeBwdArgs eb{};
-      eb.g = geom(g, nullptr);
-      eb.g_emb0 = nullptr;
-      eb.g_sh = buf(w.g_sh);
-      eb.num_gsh = 1;
-      eb.forces = forces;
-      eb.t_in = buf(w.trev);
-      eb.dvec = buf(w.dvec);
-      eb.gather = gather ? 1 : 0;
-      if (int rc = launch_edge_backward<T>(eb, stream)) return rc;
-      if (int rc = mark("edge_backward", 8.0 / sizeof(T) + 4 + c.num_bessels + double(p->D) + (gather ? 4 : 6))) return rc;
-    }
-    if (gather) {
-      ForceGatherArgs fg{N, g->rowptr, g->t_rowptr, g->t_perm, buf(w.dvec), forces};
-      if (int rc = launch_force_gather<T>(fg, stream)) return rc;
-      return mark("force_gather", 8.0 + 4.0 / sizeof(T), 3 + 8.0 / sizeof(T));
+  // Form of the one-tile pass of the fused forward (FusedForm), decided here only.  The two-waves-per-SIMD forms (aa_fused8.hip)
+  // need a plan with fused_wide, the w0 rows, and a one-tile pass (no class lists, or the mixed form).  aa_plan_options.fused_narrow:
+  //  0: boxes that leave a CU at most one workgroup (n <= 4 per CU) run one wave per SIMD whatever the kernel: there the
+  //     register-rich one-wave form -- w0 held, operands kept split -- is the faster one (64 atoms 44 vs 48 us, profiles/r06_v4_ab_c2_*).
+  //     From kFusedTailAtomsPerCu atoms per CU on, eight waves with the readout-reverse chain of the reverse pass in the tail, where
+  //     that applies (forces requested, no team pass -- its atoms would miss it -- and the chain's folded weights): there the eight-wave
+  //     form is as fast as two four-wave workgroups and the chain's 0.75 ms of streaming disappear (C4 -0.45 ms same box,
+  //     profiles/r06_v19_*).  Otherwise two four-wave workgroups per CU.
+  //  2: eight waves at any size, with the tail where it applies;  3: four waves at any size, no tail;  1: never (fused_wide is off).
+  int fused_form(const FusedFwdArgs& a, FusedForm* form) const {
+    *form = FusedForm::OneWave;
+    const bool teams = a.tile_atoms != nullptr;
+    if (!p->fused_wide || !a.w0 || (teams && !a.mixed)) return AA_OK;
+    const int cus = device_cu_count();
+    if (cus < 0) return cus;
+    const int64_t n = a.atom_end - a.atom0;
+    const bool tail_ok = want_forces && !teams && p->chain_gemm && p->o_b3af_q && p->o_b3c_q && p->cfg.num_layers == 2;
+    if (p->opt.fused_narrow == 2) {
+      *form = tail_ok ? FusedForm::EightWaveTail : FusedForm::EightWave;
+    } else if (p->opt.fused_narrow == 3) {
+      *form = FusedForm::FourWave;
+    } else if (n > int64_t(4) * cus) {
+      *form = tail_ok && n >= int64_t(kFusedTailAtomsPerCu) * cus ? FusedForm::EightWaveTail : FusedForm::FourWave;
     }
     return AA_OK;
   }
-#else
-  int backward_fused_tail(const aa_graph*, void*) { return fail(AA_ERR_INVALID, "fused reverse tail: not part of this build"); }
-#endif
 
   int forward_fused(const aa_graph* g, const void* pos, void* atom_energy) {
     const aa_model_config& c = p->cfg;
@@ -1958,10 +1864,11 @@ struct Runner {
     auto bf = [&](size_t off) { return reinterpret_cast<float*>(buf(off)); };
     a.rmax_recip = wf(p->o_rmax);
     a.bessel_w = wf(p->o_bessel);
-    a.emb_tab = wf(kFoldEmbed ? p->o_embtab_h : p->o_embtab);  // (folded: the table yields the first layer's pre-activation)
-    // the weight program of the kernel (see fused_fwd_kernel): 12-KB blocks in execution order
+    a.emb_tab = wf(p->o_embtab_h);  // (folded: the table yields the first layer's pre-activation)
+    // the weight program of the kernel (see fused_fwd_kernel): 12-KB blocks in execution order.  The plan takes the fused forward
+    // only with every fold of its program packed (aa_model_plan_create: o_embtab_h, o_g0fq, o_lat1in_fq)
     int ns = 0;
-    FusedFwdArgs* prog = &a;  // (the program under construction: `a`, later the eight-wave form's copy)
+    FusedFwdArgs* prog = &a;  // (the program under construction: `a`, later the two-waves-per-SIMD form's copy)
     auto add_layer = [&](const float* Wq, int KC, int tile0, int ntiles) {
       for (int t = tile0; t < tile0 + ntiles; t += 2)
         for (int kc = 0; kc < KC; ++kc) {
@@ -1970,35 +1877,20 @@ struct Runner {
           ++ns;
         }
     };
-    auto add_env = [&](const float* Wk) {
+    auto add_env = [&](const float* Wk) {  // one env projection: 4 blocks of env-weight rows
       for (int cblk = 0; cblk < 4; ++cblk) {
         prog->wstep[ns][0] = Wk + size_t(cblk) * 16 * p->R * 64;
         prog->wstep[ns][1] = Wk + size_t(cblk) * 16 * p->R * 64 + 1536;  // (blocks are loaded as 2 x 6 KB; 16 R 256 B are used)
         ++ns;
       }
     };
-    const bool hold = p->fused_hold_w0;
-    const bool folde = kFoldEmb1 && p->o_g0fq != 0;  // (see kFoldEmb1: no layer L1; first stage and env weights behind W1)
-    if (!kFoldEmbed) add_layer(wf(p->embed.wq[0]), 2, 0, 2);
-    if (!folde) add_layer(wf(p->embed.wq[1]), 2, 0, 2);
-    auto add_proj = [&](int l, const float* Wk) {  // one env projection: R bf16x3 64x64 layers (kProjMfma) or 4 blocks of env-weight rows
-      if (kProjMfma && p->o_wkq[l]) {
-        for (int r = 0; r < p->R; ++r) add_layer(wf(p->o_wkq[l]) + size_t(r) * gemm_bf16x3_words(64, 64), 2, 0, 2);
-      } else {
-        add_env(Wk);
-      }
-    };
-    add_proj(0, wf(folde ? p->o_wk0f : p->o_wk[0]));
-    add_layer(wf(folde ? p->o_g0fq : p->o_g0q), 2, 0, 2 + 2 * p->R);
+    add_env(wf(p->o_wk0f));
+    add_layer(wf(p->o_g0fq), 2, 0, 2 + 2 * p->R);
     add_layer(wf(p->latent[0].wq[0]), 4, 0, 2);
-    add_proj(1, wf(p->o_wk[1]));
-    const bool foldl = kFoldLatent && p->o_lat1in_fq != 0;  // (see kFoldLatent: no output layers L4 / L7, folded consumers)
-    if (!foldl) add_layer(wf(p->latent[0].wq[1]), 2, 0, 2);
-    if (!hold) add_layer(wf(folde ? p->o_g0fq : p->o_g0q), 2, 2, 2 * p->R);  // the w0 columns of the first-stage matrix again
-    add_layer(wf(foldl ? p->o_lat1in_fq : p->latent[1].wq[0]), 6, 0, 2);
-    if (!foldl) add_layer(wf(p->latent[1].wq[1]), 2, 0, 2);
-    add_layer(wf(foldl ? p->o_ro0_fq : p->readout.wq[0]), 6, 0, 2);
-    if (ns != fused_fwd_num_steps(p->R, hold) || ns > kFusedMaxSteps) return fail(AA_ERR_INVALID, "fused forward: program length mismatch");
+    add_env(wf(p->o_wk[1]));
+    add_layer(wf(p->o_lat1in_fq), 6, 0, 2);
+    add_layer(wf(p->o_ro0_fq), 6, 0, 2);
+    if (ns != fused_fwd_num_steps(p->R) || ns > kFusedMaxSteps) return fail(AA_ERR_INVALID, "fused forward: program length mismatch");
     a.tpw0 = wf(p->o_tpw[0]);
     a.tpw1 = wf(p->o_tpw[1]);
     a.coupling = c.tps[0].coupling;
@@ -2020,15 +1912,13 @@ struct Runner {
     a.x2s1 = bf(w.x2s[1]);
     a.atom_energy = static_cast<float*>(atom_energy);
     a.status = p->status;
-    a.keep = p->opt.fused_keep_split == 0 ? kFusedKeepDefault : p->opt.fused_keep_split - 1;
-    // the eight-wave form of the one-tile pass (aa_fused8.hip): its own step order -- Wenv0 | first stage | latent 0 | Wenv1 |
-    // latent 1: scal1 chunks | [lat0, two-body] chunks x {latent 1, readout} | readout: lat1 chunks
+    FusedForm form;
+    if (int rc = fused_form(a, &form)) return rc;
+    // the two-waves-per-SIMD forms of the one-tile pass (aa_fused8.hip): their own step order -- Wenv0 | first stage | latent 0 |
+    // Wenv1 | latent 1: scal1 chunks | [lat0, two-body] chunks x {latent 1, readout} | readout: lat1 chunks [| readout-reverse chain]
     FusedFwdArgs a8{};
-    const bool wide = p->fused_wide && folde && foldl && a.w0 != nullptr && (a.tile_atoms == nullptr || a.mixed);
-    if (wide) {
+    if (form != FusedForm::OneWave) {
       a8 = a;
-      a8.wide_waves = p->opt.fused_narrow == 2 ? -8 : (p->opt.fused_narrow == 3 ? -4 : 4);  // (negative: forced, also on small boxes)
-      a8.wide_one_per_cu = p->opt.fused_narrow == 6 ? 1 : 0;
       ns = 0;
       prog = &a8;
       auto add_step = [&](const float* Wq, int KC, int kc) {  // one step: the tile pair (0, 1) x chunk kc of a KC-chunk layer
@@ -2036,21 +1926,10 @@ struct Runner {
         prog->wstep[ns][1] = Wq + (size_t(1) * KC + kc) * 64 * 24;
         ++ns;
       };
-      // env projections: 4 blocks of env-weight rows (vector form), or -- fused_narrow 5, A/B -- on the matrix cores (R bf16x3 64x64
-      // layers, 2 steps each): the vector form is a quarter of the kernel's issue slots and 40 % of its LDS instructions while the
-      // matrix pipe idles, and the matrix form still measured 11 % slower (3.50 vs 3.16 ms at C4, profiles/r06_v6_ab_c4_*)
-      a8.wide_proj_mfma = (p->o_wkq[0] && p->o_wkq[1] && p->opt.fused_narrow == 5) ? 1 : 0;  // (A/B only: measured 11 % slower, HISTORY.md)
-      auto add_proj8 = [&](int l, const float* Wk) {
-        if (a8.wide_proj_mfma) {
-          for (int r = 0; r < p->R; ++r) add_layer(wf(p->o_wkq[l]) + size_t(r) * gemm_bf16x3_words(64, 64), 2, 0, 2);
-        } else {
-          add_env(Wk);
-        }
-      };
-      add_proj8(0, wf(p->o_wk0f));
+      add_env(wf(p->o_wk0f));
       add_layer(wf(p->o_g0fq), 2, 0, 2 + 2 * p->R);
       add_layer(wf(p->latent[0].wq[0]), 4, 0, 2);
-      add_proj8(1, wf(p->o_wk[1]));
+      add_env(wf(p->o_wk[1]));
       add_step(wf(p->o_lat1in_fq), 6, 4);
       add_step(wf(p->o_lat1in_fq), 6, 5);
       for (int kc : {2, 3, 0, 1}) {
@@ -2059,17 +1938,8 @@ struct Runner {
       }
       add_step(wf(p->o_ro0_fq), 6, 4);
       add_step(wf(p->o_ro0_fq), 6, 5);
-      // the readout-reverse chain (Runner::backward "B3", folded form) in the forward's tail: eight-wave form, vector projections, no
-      // team pass (its atoms would miss it), forces requested.  Taken from kFusedTailAtomsPerCu atoms per CU on (there the eight-wave
-      // form is as fast as two four-wave workgroups and the chain's 0.75 ms of streaming disappear: C4 -0.45 ms same box,
-      // profiles/r06_v19_*); fused_narrow 2 forces it, 3 / 7 keep it off.
-      const bool tail_ok = want_forces && a.tile_atoms == nullptr && !a8.wide_proj_mfma && !a8.wide_one_per_cu && p->chain_gemm && kFoldLatent &&
-                           p->o_b3af_q && p->o_b3c_q && c.num_layers == 2 && p->opt.fused_narrow != 7 && p->opt.fused_narrow != 3;
-      if (tail_ok && (a8.wide_waves == -8 || (a8.wide_waves == 4 && a.atom_end - a.atom0 >= int64_t(kFusedTailAtomsPerCu) * fused_num_cus()))) {
-        a8.wide_waves = -8;
-        a8.tail = 1;
-      }
-      if (a8.tail) {
+      const bool tail = form == FusedForm::EightWaveTail;
+      if (tail) {
         add_layer(wf(p->o_b3af_q), 2, 0, 2);
         add_layer(wf(p->o_b3bf_q ? p->o_b3bf_q : p->o_b3b_q), 4, 0, 4);
         add_layer(wf(p->o_b3c_q), 2, 0, 2);
@@ -2077,13 +1947,11 @@ struct Runner {
         a8.ld_gfcat = p->SL1;
         a8.g_scal1 = bf(w.g_scal[1]);
       }
-      if (ns != fused_fwd8_num_steps(p->R, a8.wide_proj_mfma != 0, a8.tail != 0)) return fail(AA_ERR_INVALID, "fused forward (wide): program length mismatch");
+      if (ns != fused_fwd8_num_steps(p->R, tail)) return fail(AA_ERR_INVALID, "fused forward (wide): program length mismatch");
     }
     if (int rc = mark("begin")) return rc;
-    bool ran_wide = false;
-    if (int rc = launch_fused_fwd(p->chain_pair, hold, a, stream, wide ? &a8 : nullptr, &ran_wide)) return rc;
-    fwd_b3_done = ran_wide && a8.tail;
-    if (wide && a8.tail && !ran_wide) return fail(AA_ERR_INVALID, "fused forward: the tail was planned for a launch that took the one-wave kernel");
+    if (int rc = launch_fused_fwd(p->chain_pair, form, a, form != FusedForm::OneWave ? &a8 : nullptr, stream)) return rc;
+    fwd_b3_done = form == FusedForm::EightWaveTail && a.atom_end > a.atom0;  // (an empty block launches nothing)
     // algorithmic traffic: neighbor id + shift in; unit vector, harmonics, five 64-wide rows and w0 out per edge;
     // position, two x2s blocks, energy, row pointer per atom.  Flops: the linear layers of the forward (w0 counted once).
     const double per_edge = 1 + (g->shift_vec ? 3 : 0) + 3 + 4 + p->D + 5 * 64 + p->W;
@@ -2413,7 +2281,7 @@ struct Runner {
       ca.L[2] = chain_layer(E, in, 0, wt(p->o_b3b_q), 128, S * L, c2, nullptr, nullptr, nullptr, 1, -1, 0);
       ca.L[2].a_mode = 1;
       ca.L[3] = chain_layer(E, none, 0, wt(p->o_b3c_q), 64, u, c3, nullptr, nullptr, nullptr, 1, -1, 0);
-      if (kFoldLatent && p->o_b3af_q && L == 2) {
+      if (p->o_b3af_q && L == 2) {
         // "d lat1 = d ro_h @ Wro[lat1]^T" and "d a1 = d lat1 @ Wout_1^T" as ONE 64x64 layer (folded at pack time): 12 instead of 14 steps
         ca.nlayers = 3;
         ca.L[0] = chain_layer(E, in, 0, wt(p->o_b3af_q), 64, 64, cn, nullptr, &z1, nullptr, 0, 0, 0);
@@ -2472,7 +2340,7 @@ struct Runner {
         int acc1[3] = {1, 0, 0};
         ca.L[0] = chain_layer(E, in, 0, wt(p->latent[l].wtq[1]), S, 64, cn, nullptr, &zz, &ad, 0, 0, 0);
         ca.L[1] = chain_layer(E, none, 0, wt(p->latent[l].wtq[0]), 64, S * (l + 1) + u, c1, acc1, nullptr, nullptr, 1, -1, 0);
-        if (kFoldLat0Rev && p->o_b3bf_q && L == 2 && l == 0) {
+        if (p->o_b3bf_q && L == 2 && l == 0) {
           // the readout-reverse chain already applied Wout_0^T (folded into its lat0 columns): what is left of the output layer's
           // reverse is elementwise -- d h = (d a_0 + d a_0 of the moments) x silu'(h) -- and rides as the operand transform of the
           // first-layer reverse: ONE layer, 4 steps instead of 6
@@ -2534,13 +2402,11 @@ struct Runner {
           m.ld_ga = c.latent_mlp_width;
           if (int rc = launch_tp_mom_bwd_last<T>(p->chain_pair, m, stream)) return rc;
           if (int rc = mark("tp_mom_bwd_last", p->D + W + u + 2 * m.ka1 + p->D, double(p->D) * u)) return rc;
-        } else if (use_fused_tail(g)) {
-          // (the fused reverse tail below takes it from here: layer-0 tensor product reverse + first-stage / embed-MLP reverse + edge reverse)
         } else {
           m.ld_ga = S;
           // (after a fused forward the embedding's slot holds a_e = silu(h) of scalar_embed_mlp and the env weights are folded behind
-          //  its output layer, kFoldEmb1: d a_e comes out instead of d emb)
-          if (kFoldEmb1 && p->o_wt0f && folded_fwd(g)) m.wt0 = wt(p->o_wt0f);
+          //  its output layer, fold_embed_output: d a_e comes out instead of d emb)
+          if (p->o_wt0f && folded_fwd(g)) m.wt0 = wt(p->o_wt0f);
           if (int rc = launch_tp_mom_bwd_first<T>(p->chain_pair, m, stream)) return rc;
           if (int rc = mark("tp_mom_bwd_first", p->D + 2 * W + 2 * u + 2 * m.ka0 + 2 * p->D, 2.0 * p->D * u)) return rc;
         }
@@ -2628,7 +2494,6 @@ struct Runner {
       if (int rc = launch_tp_layer_bwd<T>(p->layers[l], a, stream)) return rc;
       if (int rc = mark("tp_layer_bwd", 4 * W + 2 * p->D + 2 * u * p->D + u, 2.0 * p->D * u)) return rc;
     }
-    if (use_fused_tail(g)) return backward_fused_tail(g, forces);
     if (p->chain_gemm) {
       // first-stage reverse + scalar_embed_mlp reverse in ONE kernel
       ChainArgs ca{};
@@ -2641,8 +2506,8 @@ struct Runner {
       ca.L[0] = chain_layer(E, in, 0, wt(p->o_g0tq), p->ng0, S, cn, nullptr, nullptr, &ad, 0, 0, 0);
       ca.L[1] = chain_layer(E, none, 0, wt(p->embed.wtq[1]), S, 64, cn, nullptr, &zz, nullptr, 1, 0, 0);
       ca.L[2] = chain_layer(E, none, 0, wt(p->embed.wtq[0]), 64, c.embed_dim, ce, nullptr, nullptr, nullptr, 1, -1, 0);
-      if (kFoldEmb1 && p->o_g0tfq && folded_fwd(g)) {
-        // everything in front of the hidden layer of scalar_embed_mlp folded (kFoldEmb1; the forward stored a_e, not the embedding):
+      if (p->o_g0tfq && folded_fwd(g)) {
+        // everything in front of the hidden layer of scalar_embed_mlp folded (fold_embed_output; the forward stored a_e, not the embedding):
         // d h = ((d[two-body | w0] @ (W1 G0)^T) + d a_e of the moments) x silu'(h) -- ONE 256 -> 64 layer, 8 steps -- ...
         ca.nlayers = 1;
         ca.L[0] = chain_layer(E, in, 0, wt(p->o_g0tfq), p->ng0, 64, cn, nullptr, &zz, &ad, 0, 0, 0);
@@ -2660,7 +2525,7 @@ struct Runner {
           ca.L[1] = chain_layer(E, none, 0, wt(p->embed.wtq[0]), 64, c.embed_dim, ce, nullptr, nullptr, nullptr, 1, -1, 0);
         }
       } else if (p->embed_fused && p->o_embtab_h) {
-        // folded table (kFoldEmbed): d_h, the output of the second layer, is contracted straight back to the 8 basis functions
+        // folded table (fold_embed_table): d_h, the output of the second layer, is contracted straight back to the 8 basis functions
         // with T = tab @ W0 -- the layer W0^T and d emb0 do not exist
         ca.nlayers = 2;
         ca.L[1].embrev_out = buf(w.trev);

@@ -280,17 +280,10 @@ typedef struct {
   int32_t embed_no_fuse;   /* reverse pass: materialise d(two-body embedding)                                   */
   int32_t fused_forward;   /* fused per-atom-tile forward: 0 / 1 whenever aa_graph.max_degree allows; 3 never (staged pipeline);
                             * A/B: 2 / 4 = for every graph with segments <= 128 in the pure team / the mixed form */
-  int32_t fused_recompute_w0; /* fused forward: recompute w0 for the second layer instead of holding it         */
   int32_t moments_waves_per_block; /* 0 = 1                                                                      */
   int32_t f64_rows;        /* fp64 linear layers, row-resident kernels (operand rows read once): 0 where measured faster, 1 wherever applicable, 2 off */
   int32_t no_channel_padding; /* stacks whose channel count is not a multiple of 64, or with single hidden layers narrower than
                                * 64, are normally evaluated zero-padded (same results, tuned kernels); 1: keep them narrow */
-  int32_t fused_tail;      /* experimental builds only (AA_BUILD_EXPERIMENTAL=1): 1 = the fused per-atom-tile
-                            * reverse tail (aa_fused_bwd.hip) where the fused forward runs, 2 = ... leaving the edge reverse to
-                            * edge_backward; measured slower than the staged tail on MI355X, ignored by the product build      */
-  int32_t fused_keep_split; /* fused forward, one-tile form: tile pairs that feed several layers are split into their bf16 levels once and
-                             * held in registers: 0 = the default (2), 1 = none (parked raw in LDS, split by every reader), 2 = the two-body
-                             * scalars, 3 = two-body scalars and lat0 */
   int32_t poison_workspace; /* debugging: every step first fills the whole workspace with 0xFF bytes (NaN in fp32 and fp64), so
                              * that a kernel reading a cell no earlier kernel of the SAME step wrote shows up as NaN       */
   int32_t no_slot_form;     /* operator-kernel plans (e.g. fp64, l_max 3, 3 layers): 1 = the unfolded single-layer pipeline instead of
@@ -308,11 +301,12 @@ typedef struct {
                              * by the forward's energy reduction, which reads the same rows (A/B, tests)                          */
   int32_t tp_prefer_moments; /* 2-layer u = 64 stacks the fused chains do not cover (fp64; S or MLP widths of 128): 1 = the 2-layer moments
                               * kernels + single linear layers (the selection up to round 4) instead of the operator kernels (A/B, tests) */
-  int32_t fused_narrow;     /* fused forward, one-tile pass, where the two-waves-per-SIMD form applies (aa_fused8.hip: one species, folded
-                             * program): 0 = that form as two independent four-wave workgroups per CU, 2 = as one eight-wave workgroup per CU
-                             * (lock step), 1 = the one-wave-per-SIMD kernel of rounds 2-5 (A/B, tests).  Boxes of at most 4 atoms per CU take the
-                             * round 2-5 kernel under 0 (every CU holds at most one workgroup anyway); 3 = the four-wave form there too (tests); 5 = 3 with the env
-                             * projections as bf16x3 layers on the matrix cores (A/B: measured slower) */
+  int32_t fused_narrow;     /* fused forward, one-tile pass, where the two-waves-per-SIMD form applies (aa_fused8.hip: one species):
+                             * 0 = automatic: boxes of at most 4 atoms per CU take the one-wave-per-SIMD kernel (every CU holds at most one
+                             * workgroup anyway), from 64 atoms per CU on one eight-wave workgroup per CU with the readout-reverse chain in its
+                             * tail (forces requested, no team pass), else two independent four-wave workgroups per CU; 1 = the
+                             * one-wave-per-SIMD kernel of rounds 2-5 (A/B, tests); 2 = the eight-wave form at any size, with the tail where
+                             * it applies (tests); 3 = the four-wave form at any size, no tail (tests) */
   int32_t chain_staged_weights; /* one-layer reverse chains: 1 = the per-workgroup weight staging of the general chain kernel also where the
                                  * persistent form with LDS-resident weights applies (round 6; A/B, tests)                               */
 } aa_plan_options;
