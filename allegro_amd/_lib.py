@@ -89,6 +89,31 @@ class Graph(C.Structure):
                 ("max_degree", C.c_int64)]
 
 
+class GemmSeg(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("ld", C.c_int32), ("n", C.c_int32)]
+
+
+class GemmDesc(C.Structure):
+    """`aa_gemm_desc` of the test hook aa_debug_gemm: one linear layer with the full argument surface of launch_gemm."""
+    _fields_ = [("dtype", C.c_int32), ("K", C.c_int32), ("N", C.c_int32), ("M", C.c_int64),
+                ("a_count", C.c_int32), ("c_count", C.c_int32), ("a", GemmSeg * 3), ("c", GemmSeg * 3),
+                ("c_accum", C.c_int32 * 3), ("has_z", C.c_int32), ("has_add", C.c_int32), ("z", GemmSeg * 3),
+                ("add", GemmSeg * 3), ("act_a", C.c_int32), ("act_lo", C.c_int32), ("act_hi", C.c_int32),
+                ("act_kind", C.c_int32), ("batch", C.c_int32), ("a_bs", C.c_int64), ("c_bs", C.c_int64),
+                ("bsel4", C.c_uint64), ("num_weights", C.c_int32), ("weights", C.c_void_p), ("force_kernel", C.c_int32),
+                ("v1", C.c_int32), ("lds_epilogue", C.c_int32), ("f64_rows", C.c_int32), ("f64_column_loop", C.c_int32)]
+
+
+# aa_gemm_form: the kernel forms of a linear layer (include/allegro_amd.h; tests/test_gemm_forms.py checks the two agree)
+GEMM_FORMS = {name: i for i, name in enumerate((
+    "NONE",
+    "F64_VALU", "F64_MFMA", "F64_PIPE_GRID", "F64_PIPE_LOOP", "F64_ROWS_ACC", "F64_ROWS_OPND", "F64_ROWS_ACC_BATCHED",
+    "F64_ROWS_OPND_BATCHED", "F64_VALU_EACH", "F64_MFMA_EACH", "F64_PIPE_GRID_EACH", "F64_PIPE_LOOP_EACH",
+    "F32_VALU", "F32_MFMA_V1", "F32_V3_K2", "F32_V3_K4", "F32_V3_KS", "F32_BF16X3_K2", "F32_BF16X3_K4", "F32_BF16X3_KS",
+    "F32_BF16X3_LDS_K2", "F32_BF16X3_LDS_K4", "F32_BF16X3_LDS_KS", "F32_BF16X3_BATCHED_K2", "F32_BF16X3_BATCHED_K4",
+    "F32_BF16X3_BATCHED_KS", "F32_VALU_EACH", "F32_MFMA_V1_EACH", "F32_V3_EACH", "F32_BF16X3_LDS_EACH"))}
+
+
 class AllegroError(RuntimeError):
     pass
 
@@ -166,6 +191,8 @@ class AllegroLib:
         L.aa_act_derivative_pair.restype = C.c_int
         L.aa_debug_gemm_f32.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.aa_debug_gemm_f32.restype = C.c_int
+        L.aa_debug_gemm.argtypes = [C.POINTER(GemmDesc), C.POINTER(C.c_int32), C.c_void_p]
+        L.aa_debug_gemm.restype = C.c_int
         L.aa_model_plan_create.argtypes = [C.POINTER(ModelConfig), C.POINTER(C.c_void_p)]
         L.aa_model_plan_create_with_options.argtypes = [C.POINTER(ModelConfig), C.POINTER(PlanOptions), C.POINTER(C.c_void_p)]
         L.aa_model_plan_destroy.argtypes = [C.c_void_p]

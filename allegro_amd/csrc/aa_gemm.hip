@@ -38,6 +38,7 @@ __device__ __forceinline__ void seg_store(const GemmArgs& g, int64_t row, int co
   for (int s = 0; s < 3; ++s) {
     if (s < g.c.count) {
       if (c < g.c.s[s].n) {
+        if (!g.c.s[s].p) return;  // (a null segment is computed but not stored)
         if (g.has_add) v += static_cast<const T*>(g.add.s[s].p)[row * g.add.s[s].ld + c];
         if (g.has_z) {
           T z = static_cast<const T*>(g.z.s[s].p)[row * g.z.s[s].ld + c];
@@ -755,7 +756,7 @@ __device__ __forceinline__ void store_tile_t(const GemmArgs& g, const v16f& acc,
     const Dst4 d = resolve4(g, gm, f0, c_shift);
     if (d.nvalid == 0) continue;
     v4f v = {acc[4 * gq], acc[4 * gq + 1], acc[4 * gq + 2], acc[4 * gq + 3]};
-    if (vec_ok && d.nvalid == 4) {
+    if (vec_ok && d.nvalid == 4 && d.c) {
       if (d.add) {
         const v4f ad = *reinterpret_cast<const v4f*>(d.add);
 #pragma unroll
@@ -774,14 +775,19 @@ __device__ __forceinline__ void store_tile_t(const GemmArgs& g, const v16f& acc,
       *reinterpret_cast<v4f*>(d.c) = v;
     } else {
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (e < d.nvalid) {
-          float x = v[e];
-          if (d.add) x += d.add[e];
-          if (d.z) x *= dsilu(d.z[e]);
-          if (d.accum) x += d.c[e];
-          d.c[e] = x;
-        }
+      for (int e = 0; e < 4; ++e) {
+        // a group that straddles C segments (a width not a multiple of 4): the features past nvalid belong to the next
+        // segment(s) and are resolved on their own; a null segment is computed but not stored
+        const bool own = e < d.nvalid;
+        const Dst4 de = own ? d : resolve4(g, gm, f0 + e, c_shift);
+        const int o = own ? e : 0;
+        if (de.nvalid == 0 || !de.c) continue;
+        float x = v[e];
+        if (de.add) x += de.add[o];
+        if (de.z) x *= dsilu(de.z[o]);
+        if (de.accum) x += de.c[o];
+        de.c[o] = x;
+      }
     }
   }
 }
@@ -812,7 +818,7 @@ __device__ __forceinline__ void store_pair_lds(const GemmArgs& g, const v16f& ac
     const int64_t gm = m0 + r;
     if (!col_ok) continue;
     const Dst4 d = resolve4(g, gm, f0);
-    if (d.nvalid != 4) continue;  // (segments are 4-granular on this path)
+    if (d.nvalid != 4 || !d.c) continue;  // (segments are 4-granular on this path; a null segment is not stored)
     v4f v = *reinterpret_cast<const v4f*>(patch + r * EP_LD + c4);
     if (d.add) {
       const v4f ad = *reinterpret_cast<const v4f*>(d.add);
@@ -1778,63 +1784,123 @@ static int launch_gemm_each(const GemmArgs& g, hipStream_t stream) {
   return AA_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Form selection: which kernel (and launch shape) runs a linear layer is decided HERE and nowhere else; launch_gemm only
+// carries the decision out.  The forms are listed in include/allegro_amd.h (aa_gemm_form, reported by aa_debug_gemm).
+// ---------------------------------------------------------------------------------------------
+
+// 16-B epilogue accesses of the fp32 MFMA kernels need every C / z / add segment to be 4-column granular and 16-B aligned
+static int epilogue_vec_ok(const GemmArgs& g) {
+  int vec_ok = 1;
+  for (int s = 0; s < g.c.count; ++s) {
+    if ((g.c.s[s].n & 3) || (g.c.s[s].ld & 3) || (reinterpret_cast<uintptr_t>(g.c.s[s].p) & 15)) vec_ok = 0;
+    if (g.has_z && ((g.z.s[s].ld & 3) || (reinterpret_cast<uintptr_t>(g.z.s[s].p) & 15))) vec_ok = 0;
+    if (g.has_add && ((g.add.s[s].ld & 3) || (reinterpret_cast<uintptr_t>(g.add.s[s].p) & 15))) vec_ok = 0;
+  }
+  return vec_ok;
+}
+
+// a batch on a kernel without the batched form: one launch per problem (launch_gemm_each)
+static bool gemm_form_each(aa_gemm_form f) {
+  return (f >= AA_GEMM_F64_VALU_EACH && f <= AA_GEMM_F64_PIPE_LOOP_EACH) || (f >= AA_GEMM_F32_VALU_EACH && f <= AA_GEMM_F32_BF16X3_LDS_EACH);
+}
+
+template <typename T>
+aa_gemm_form gemm_form(const GemmArgs& g);
+
+// (arguments already accepted by check_args)
+template <>
+aa_gemm_form gemm_form<float>(const GemmArgs& g) {
+  if (g.M == 0) return AA_GEMM_FORM_NONE;
+  const bool each = g.batch > 1;
+  if (g.force_kernel == 3 || g.act_kind != AA_ACT_SILU) return each ? AA_GEMM_F32_VALU_EACH : AA_GEMM_F32_VALU;
+  // v3 / bf16x3 fetch the operand rows in 16-column fragments: every A segment 16-column granular with 16-B aligned rows
+  if (!g.Bp || g.opt_v1 || !seglist_frag_ok_host(g.a)) return each ? AA_GEMM_F32_MFMA_V1_EACH : AA_GEMM_F32_MFMA_V1;
+  const int KC = (g.K + 31) / 32;
+  const int kv = KC <= 2 ? 0 : (KC <= 4 ? 1 : 2);  // operand fragments held for K <= 64 / 128, streamed beyond
+  bool seg32 = true;  // bf16x3 fetches 32-column fragments
+  for (int q = 0; q < g.a.count; ++q) seg32 = seg32 && (g.a.s[q].n % 32 == 0);
+  if (g.Bq && g.force_kernel != 1 && seg32) {
+    // default: direct epilogue (the LDS-transposed variant measured slower); the LDS one needs the 16-B epilogue accesses
+    if (epilogue_vec_ok(g) && g.opt_lds_epilogue != 0) return each ? AA_GEMM_F32_BF16X3_LDS_EACH : aa_gemm_form(AA_GEMM_F32_BF16X3_LDS_K2 + kv);
+    return aa_gemm_form((each ? AA_GEMM_F32_BF16X3_BATCHED_K2 : AA_GEMM_F32_BF16X3_K2) + kv);
+  }
+  return each ? AA_GEMM_F32_V3_EACH : aa_gemm_form(AA_GEMM_F32_V3_K2 + kv);
+}
+
+template <>
+aa_gemm_form gemm_form<double>(const GemmArgs& g) {
+  if (g.M == 0) return AA_GEMM_FORM_NONE;
+  const bool each = g.batch > 1;  // (only the row-resident kernels have the batched form)
+  if (g.force_kernel == 3 || g.act_kind != AA_ACT_SILU) return each ? AA_GEMM_F64_VALU_EACH : AA_GEMM_F64_VALU;
+  // pipelined and row-resident kernels: 16-B operand and weight loads, every A and C segment a multiple of 16 columns wide
+  // (hence K % 16 == 0 and N % 16 == 0: a 16-column tile or chunk never straddles a segment)
+  bool pipe_ok = (g.K % 16) == 0 && (g.N % 16) == 0 && (reinterpret_cast<uintptr_t>(g.B) & 15) == 0;
+  for (int s2 = 0; s2 < g.a.count; ++s2)
+    pipe_ok = pipe_ok && (g.a.s[s2].n % 16) == 0 && (g.a.s[s2].ld % 2) == 0 && (reinterpret_cast<uintptr_t>(g.a.s[s2].p) & 15) == 0;
+  bool epilogue_reads = g.has_z || g.has_add;  // operands the epilogue has to FETCH (z, add, accumulated-into C)
+  for (int s2 = 0; s2 < g.c.count; ++s2) {
+    pipe_ok = pipe_ok && (g.c.s[s2].n % 16) == 0;
+    epilogue_reads = epilogue_reads || g.c_accum[s2] != 0;
+  }
+  if (!pipe_ok) return each ? AA_GEMM_F64_MFMA_EACH : AA_GEMM_F64_MFMA;
+  // row-resident kernels (gemm_f64_rows_kernel): every operand row is read from HBM once; accumulator-resident for N <= 128
+  // (a wave holds its 32 x N output), operand-resident for K <= 128 (a wave holds its 32 x K operand rows).  Measured at C5
+  // (1.7 M rows; profiles/archive/r03_*_stages_c5.log, after the epilogue loads were batched and the operand activation
+  // deferred): the accumulator-resident form wins everywhere, 54-58 vs 45-52 TFLOP/s for K > 128 and 5-10 % on 128 x 128
+  // layers with or without z / add operands; the operand-resident form (N > 128, K <= 128) wins 5-8 % on plain layers and
+  // loses 25-30 % where the epilogue fetches z / add operands or accumulates into C (its two waves per SIMD overlap the
+  // silu' arithmetic of one pass with the next pass's MFMAs worse than the staged kernel's three) -- those keep the staged
+  // kernel unless forced (aa_plan_options.f64_rows: 1 wherever applicable, 2 never).
+  const bool rows_ok = g.opt_f64_column_loop == 0 && g.opt_f64_rows != 2 &&
+                       (g.opt_f64_rows == 1 ? (g.N <= 128 || g.K <= 128) : (g.N <= 128 || (g.K <= 128 && !epilogue_reads)));
+  if (rows_ok) {
+    if (g.N <= 128) return each ? AA_GEMM_F64_ROWS_ACC_BATCHED : AA_GEMM_F64_ROWS_ACC;
+    return each ? AA_GEMM_F64_ROWS_OPND_BATCHED : AA_GEMM_F64_ROWS_OPND;
+  }
+  // enough row tiles to fill the chip on their own: one workgroup per row tile looping over the column tiles
+  // (aa_plan_options.f64_column_loop: 1 never, 2 always -- tests)
+  const int64_t row_tiles = (g.M + G6_BM - 1) / G6_BM;
+  if (g.opt_f64_column_loop == 2 || (g.opt_f64_column_loop == 0 && row_tiles >= 2048)) return each ? AA_GEMM_F64_PIPE_LOOP_EACH : AA_GEMM_F64_PIPE_LOOP;
+  return each ? AA_GEMM_F64_PIPE_GRID_EACH : AA_GEMM_F64_PIPE_GRID;
+}
+
 template <>
 int launch_gemm<float>(const GemmArgs& g, hipStream_t stream) {
   if (g.M == 0) return AA_OK;
   if (int rc = check_args(g)) return rc;
-  const bool v1_only = g.opt_v1 != 0;
-  if (g.force_kernel == 3 || g.act_kind != AA_ACT_SILU) {
-    if (g.batch > 1) return launch_gemm_each<float>(g, stream);
-    dim3 grid((unsigned)((g.M + GV_BM - 1) / GV_BM), (unsigned)((g.N + GV_BN - 1) / GV_BN));
-    size_t smem = sizeof(float) * (GV_BK * GV_LDA + GV_BK * GV_BN);
-    hipLaunchKernelGGL(gemm_valu_kernel<float>, grid, dim3(256), smem, stream, g);
-  } else if (g.Bp && !v1_only && seglist_frag_ok_host(g.a)) {
-    dim3 grid((unsigned)((g.M + 127) / 128));
-    // 16-B epilogue accesses need every C/Z segment to be 4-column granular and 16-B aligned
-    int vec_ok = 1;
-    for (int s = 0; s < g.c.count; ++s) {
-      if ((g.c.s[s].n & 3) || (g.c.s[s].ld & 3) || (reinterpret_cast<uintptr_t>(g.c.s[s].p) & 15)) vec_ok = 0;
-      if (g.has_z && ((g.z.s[s].ld & 3) || (reinterpret_cast<uintptr_t>(g.z.s[s].p) & 15))) vec_ok = 0;
-      if (g.has_add && ((g.add.s[s].ld & 3) || (reinterpret_cast<uintptr_t>(g.add.s[s].p) & 15))) vec_ok = 0;
+  const aa_gemm_form f = gemm_form<float>(g);
+  if (gemm_form_each(f)) return launch_gemm_each<float>(g, stream);
+  const int vec_ok = epilogue_vec_ok(g);
+  const u32x4* Wq = static_cast<const u32x4*>(g.Bq);
+  const dim3 grid((unsigned)((g.M + 127) / 128), 1, g.batch > 1 ? unsigned(g.batch) : 1u);  // (v3 / bf16x3: 128-row tiles)
+  const size_t smem_lds = sizeof(float) * 4 * 32 * EP_LD;
+  switch (f) {
+    case AA_GEMM_F32_VALU: {
+      dim3 gridv((unsigned)((g.M + GV_BM - 1) / GV_BM), (unsigned)((g.N + GV_BN - 1) / GV_BN));
+      size_t smem = sizeof(float) * (GV_BK * GV_LDA + GV_BK * GV_BN);
+      hipLaunchKernelGGL(gemm_valu_kernel<float>, gridv, dim3(256), smem, stream, g);
+      break;
     }
-    const int KC = (g.K + 31) / 32;
-    const bool direct_epi = g.opt_lds_epilogue == 0;  // default: direct (the LDS-transposed variant measured slower)
-    bool seg32 = true;
-    for (int q = 0; q < g.a.count; ++q) seg32 = seg32 && (g.a.s[q].n % 32 == 0);
-    if (g.Bq && g.force_kernel != 1 && seg32) {
-      const u32x4* Wq = static_cast<const u32x4*>(g.Bq);
-      const bool lds = vec_ok && !direct_epi;
-      if (g.batch > 1) {
-        if (lds) return launch_gemm_each<float>(g, stream);
-        grid.z = unsigned(g.batch);  // (the direct-epilogue kernel has the batched form)
-      }
-      const size_t smem = lds ? sizeof(float) * 4 * 32 * EP_LD : 0;
-#define AA_LAUNCH_BF16(KCR)                                                                                   \
-  if (lds)                                                                                                    \
-    hipLaunchKernelGGL((gemm_bf16x3_kernel<KCR, true>), grid, dim3(256), smem, stream, g, Wq, vec_ok);        \
-  else                                                                                                        \
-    hipLaunchKernelGGL((gemm_bf16x3_kernel<KCR, false>), grid, dim3(256), smem, stream, g, Wq, vec_ok);
-      if (KC <= 2) {
-        AA_LAUNCH_BF16(2)
-      } else if (KC <= 4) {
-        AA_LAUNCH_BF16(4)
-      } else {
-        AA_LAUNCH_BF16(0)
-      }
-#undef AA_LAUNCH_BF16
-    } else if (g.batch > 1)
-      return launch_gemm_each<float>(g, stream);
-    else if (KC <= 2)
-      hipLaunchKernelGGL(gemm_mfma_f32_v3_kernel<2>, grid, dim3(256), 0, stream, g, vec_ok);
-    else if (KC <= 4)
-      hipLaunchKernelGGL(gemm_mfma_f32_v3_kernel<4>, grid, dim3(256), 0, stream, g, vec_ok);
-    else
-      hipLaunchKernelGGL(gemm_mfma_f32_v3_kernel<0>, grid, dim3(256), 0, stream, g, vec_ok);
-  } else {
-    if (g.batch > 1) return launch_gemm_each<float>(g, stream);
-    dim3 grid((unsigned)((g.M + GM_BM - 1) / GM_BM), (unsigned)((g.N + GM_BN - 1) / GM_BN));
-    size_t smem = sizeof(float) * (GM_BK * GM_LDA + GM_BK * GM_BN);
-    hipLaunchKernelGGL(gemm_mfma_f32_kernel, grid, dim3(256), smem, stream, g);
+    case AA_GEMM_F32_MFMA_V1: {
+      dim3 grid1((unsigned)((g.M + GM_BM - 1) / GM_BM), (unsigned)((g.N + GM_BN - 1) / GM_BN));
+      size_t smem = sizeof(float) * (GM_BK * GM_LDA + GM_BK * GM_BN);
+      hipLaunchKernelGGL(gemm_mfma_f32_kernel, grid1, dim3(256), smem, stream, g);
+      break;
+    }
+    case AA_GEMM_F32_V3_K2: hipLaunchKernelGGL(gemm_mfma_f32_v3_kernel<2>, grid, dim3(256), 0, stream, g, vec_ok); break;
+    case AA_GEMM_F32_V3_K4: hipLaunchKernelGGL(gemm_mfma_f32_v3_kernel<4>, grid, dim3(256), 0, stream, g, vec_ok); break;
+    case AA_GEMM_F32_V3_KS: hipLaunchKernelGGL(gemm_mfma_f32_v3_kernel<0>, grid, dim3(256), 0, stream, g, vec_ok); break;
+    case AA_GEMM_F32_BF16X3_K2:
+    case AA_GEMM_F32_BF16X3_BATCHED_K2: hipLaunchKernelGGL((gemm_bf16x3_kernel<2, false>), grid, dim3(256), 0, stream, g, Wq, vec_ok); break;
+    case AA_GEMM_F32_BF16X3_K4:
+    case AA_GEMM_F32_BF16X3_BATCHED_K4: hipLaunchKernelGGL((gemm_bf16x3_kernel<4, false>), grid, dim3(256), 0, stream, g, Wq, vec_ok); break;
+    case AA_GEMM_F32_BF16X3_KS:
+    case AA_GEMM_F32_BF16X3_BATCHED_KS: hipLaunchKernelGGL((gemm_bf16x3_kernel<0, false>), grid, dim3(256), 0, stream, g, Wq, vec_ok); break;
+    case AA_GEMM_F32_BF16X3_LDS_K2: hipLaunchKernelGGL((gemm_bf16x3_kernel<2, true>), grid, dim3(256), smem_lds, stream, g, Wq, vec_ok); break;
+    case AA_GEMM_F32_BF16X3_LDS_K4: hipLaunchKernelGGL((gemm_bf16x3_kernel<4, true>), grid, dim3(256), smem_lds, stream, g, Wq, vec_ok); break;
+    case AA_GEMM_F32_BF16X3_LDS_KS: hipLaunchKernelGGL((gemm_bf16x3_kernel<0, true>), grid, dim3(256), smem_lds, stream, g, Wq, vec_ok); break;
+    default: return fail(AA_ERR_INVALID, "gemm: no fp32 kernel for the selected form");
   }
   AA_CHECK_HIP(hipGetLastError());
   return AA_OK;
@@ -1844,46 +1910,30 @@ template <>
 int launch_gemm<double>(const GemmArgs& g, hipStream_t stream) {
   if (g.M == 0) return AA_OK;
   if (int rc = check_args(g)) return rc;
-  dim3 grid((unsigned)((g.M + GV_BM - 1) / GV_BM), (unsigned)((g.N + GV_BN - 1) / GV_BN));
-  size_t smem = sizeof(double) * (GV_BK * GV_LDA + GV_BK * GV_BN);
-  bool pipe_ok = (g.N % 2) == 0 && (reinterpret_cast<uintptr_t>(g.B) & 15) == 0;
-  for (int s2 = 0; s2 < g.a.count; ++s2)
-    pipe_ok = pipe_ok && (g.a.s[s2].n % 16) == 0 && (g.a.s[s2].ld % 2) == 0 && (reinterpret_cast<uintptr_t>(g.a.s[s2].p) & 15) == 0;
-  bool epilogue_reads = g.has_z || g.has_add;  // operands the epilogue has to FETCH (z, add, accumulated-into C)
-  for (int s2 = 0; s2 < g.c.count; ++s2) {
-    pipe_ok = pipe_ok && (g.c.s[s2].n % 16) == 0;
-    epilogue_reads = epilogue_reads || g.c_accum[s2] != 0;
-  }
-  const bool rows_ok = pipe_ok && g.opt_f64_column_loop == 0 && g.opt_f64_rows != 2 && (g.K % 16) == 0 &&
-                       (g.opt_f64_rows == 1 ? (g.N <= 128 || g.K <= 128) : (g.N <= 128 || (g.K <= 128 && !epilogue_reads)));
-  if (g.batch > 1 && (g.force_kernel == 3 || g.act_kind != AA_ACT_SILU || !rows_ok)) return launch_gemm_each<double>(g, stream);  // (only the row-resident kernels have the batched form)
-  if (g.force_kernel == 3 || g.act_kind != AA_ACT_SILU) {
-    hipLaunchKernelGGL(gemm_valu_kernel<double>, grid, dim3(256), smem, stream, g);
-  } else if (pipe_ok && g.opt_f64_column_loop == 0 && g.opt_f64_rows != 2 && (g.K % 16) == 0 &&
-             (g.opt_f64_rows == 1 ? (g.N <= 128 || g.K <= 128) : (g.N <= 128 || (g.K <= 128 && !epilogue_reads)))) {
-    // row-resident kernels: every operand row is read from HBM once.  Measured at C5 (1.7 M rows; profiles/archive/r03_*_stages_c5.log,
-    // after the epilogue loads were batched and the operand activation deferred): the accumulator-resident form (N <= 128)
-    // wins everywhere, 54-58 vs 45-52 TFLOP/s for K > 128 and 5-10 % on 128 x 128 layers with or without z / add operands;
-    // the operand-resident form (N > 128, K <= 128) wins 5-8 % on plain layers and loses 25-30 % where the epilogue fetches
-    // z / add operands or accumulates into C (its two waves per SIMD overlap the silu' arithmetic of one pass with the next pass's MFMAs worse
-    // than the staged kernel's three) -- those keep the staged kernel unless forced (aa_plan_options.f64_rows = 1).
-    dim3 gridr((unsigned)((g.M + 127) / 128), 1, g.batch > 1 ? unsigned(g.batch) : 1u);
-    if (g.N <= 128) {
-      const size_t smemr = sizeof(double) * 2 * 16 * (128 + 4);
-      hipLaunchKernelGGL(gemm_f64_rows_kernel<false>, gridr, dim3(256), smemr, stream, g);
-    } else {
-      const size_t smemr = sizeof(double) * 2 * 16 * (64 + 4);
-      hipLaunchKernelGGL(gemm_f64_rows_kernel<true>, gridr, dim3(256), smemr, stream, g);
-    }
-  } else if (pipe_ok) {
-    dim3 grid6((unsigned)((g.M + G6_BM - 1) / G6_BM), (unsigned)((g.N + G6_BN - 1) / G6_BN));
-    // enough row tiles to fill the chip on their own: one workgroup per row tile looping over the column tiles
-    // (aa_plan_options.f64_column_loop: 1 never, 2 always -- tests)
-    if (g.opt_f64_column_loop == 2 || (g.opt_f64_column_loop == 0 && grid6.x >= 2048)) grid6.y = 1;
-    const size_t smem6 = sizeof(double) * 2 * (G6_BK * G6_LDA + G6_BK * G6_BN);
-    hipLaunchKernelGGL(gemm_mfma_f64_pipe_kernel, grid6, dim3(256), smem6, stream, g);
-  } else {
-    hipLaunchKernelGGL(gemm_mfma_f64_kernel, grid, dim3(256), smem, stream, g);
+  const aa_gemm_form f = gemm_form<double>(g);
+  if (gemm_form_each(f)) return launch_gemm_each<double>(g, stream);
+  const dim3 grid((unsigned)((g.M + GV_BM - 1) / GV_BM), (unsigned)((g.N + GV_BN - 1) / GV_BN));
+  const size_t smem = sizeof(double) * (GV_BK * GV_LDA + GV_BK * GV_BN);
+  const dim3 gridr((unsigned)((g.M + 127) / 128), 1, g.batch > 1 ? unsigned(g.batch) : 1u);
+  dim3 grid6((unsigned)((g.M + G6_BM - 1) / G6_BM), (unsigned)((g.N + G6_BN - 1) / G6_BN));
+  const size_t smem6 = sizeof(double) * 2 * (G6_BK * G6_LDA + G6_BK * G6_BN);
+  switch (f) {
+    case AA_GEMM_F64_VALU: hipLaunchKernelGGL(gemm_valu_kernel<double>, grid, dim3(256), smem, stream, g); break;
+    case AA_GEMM_F64_MFMA: hipLaunchKernelGGL(gemm_mfma_f64_kernel, grid, dim3(256), smem, stream, g); break;
+    case AA_GEMM_F64_ROWS_ACC:
+    case AA_GEMM_F64_ROWS_ACC_BATCHED:
+      hipLaunchKernelGGL(gemm_f64_rows_kernel<false>, gridr, dim3(256), sizeof(double) * 2 * 16 * (128 + 4), stream, g);
+      break;
+    case AA_GEMM_F64_ROWS_OPND:
+    case AA_GEMM_F64_ROWS_OPND_BATCHED:
+      hipLaunchKernelGGL(gemm_f64_rows_kernel<true>, gridr, dim3(256), sizeof(double) * 2 * 16 * (64 + 4), stream, g);
+      break;
+    case AA_GEMM_F64_PIPE_LOOP:
+      grid6.y = 1;  // (gridDim.y == 1: the kernel walks every column tile)
+      hipLaunchKernelGGL(gemm_mfma_f64_pipe_kernel, grid6, dim3(256), smem6, stream, g);
+      break;
+    case AA_GEMM_F64_PIPE_GRID: hipLaunchKernelGGL(gemm_mfma_f64_pipe_kernel, grid6, dim3(256), smem6, stream, g); break;
+    default: return fail(AA_ERR_INVALID, "gemm: no fp64 kernel for the selected form");
   }
   AA_CHECK_HIP(hipGetLastError());
   return AA_OK;
@@ -2028,4 +2078,102 @@ extern "C" int aa_debug_gemm_f32(int kernel, int64_t M, int K, int N, const floa
   if (rc == AA_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(AA_ERR_HIP, "aa_debug_gemm_f32: kernel failed");
   cleanup();
   return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// test hook (include/allegro_amd.h, "debug entry points"): one linear layer through launch_gemm with every argument the
+// model's layers can pass -- segments, epilogue operands, activation range, batches, plan options -- reporting the form
+// gemm_form chose, so that each form can be bounded directly against a high-precision product
+// ---------------------------------------------------------------------------------------------
+namespace {
+template <typename T>
+int debug_gemm(const aa_gemm_desc& d, int32_t* form, hipStream_t s) {
+  using namespace aa;
+  const int K = d.K, N = d.N, nw = d.num_weights;
+  auto seglist = [](const aa_gemm_seg* in, int count) {
+    SegList l{};
+    l.count = count;
+    for (int q = 0; q < count; ++q) l.s[q] = Seg{in[q].p, in[q].ld, in[q].n};
+    return l;
+  };
+  GemmArgs g{};
+  g.M = d.M;
+  g.K = K;
+  g.N = N;
+  g.a = seglist(d.a, d.a_count);
+  g.c = seglist(d.c, d.c_count);
+  for (int q = 0; q < 3; ++q) g.c_accum[q] = d.c_accum[q];
+  g.has_z = d.has_z != 0;
+  if (g.has_z) g.z = seglist(d.z, d.c_count);
+  g.has_add = d.has_add != 0;
+  if (g.has_add) g.add = seglist(d.add, d.c_count);
+  g.act_a = d.act_a;
+  g.act_lo = d.act_lo;
+  g.act_hi = d.act_hi;
+  g.act_kind = d.act_kind;
+  g.force_kernel = d.force_kernel;
+  g.opt_v1 = d.v1;
+  g.opt_lds_epilogue = d.lds_epilogue;
+  g.opt_f64_rows = d.f64_rows;
+  g.opt_f64_column_loop = d.f64_column_loop;
+  g.batch = d.batch;
+  g.a_bs = d.a_bs;
+  g.c_bs = d.c_bs;
+  g.bsel4 = d.bsel4;
+  // the weight set as the model packs it: plain [K][N], fp32 MFMA fragment order, bf16x3 levels (fp32 only)
+  constexpr bool f32 = std::is_same<T, float>::value;
+  const size_t nplain = size_t(K) * N, np = f32 ? gemm_packed_elems(K, N) : 0, nq = f32 ? gemm_bf16x3_words(K, N) : 0;
+  const T* W = static_cast<const T*>(d.weights);
+  std::vector<T> wp(nw * np);
+  std::vector<unsigned> wq(nw * nq);
+  if constexpr (f32) {
+    std::vector<double> wd(nplain), wpd(np);
+    for (int m = 0; m < nw; ++m) {
+      std::copy(W + m * nplain, W + (m + 1) * nplain, wd.begin());
+      gemm_pack_b(wd.data(), K, N, wpd.data());
+      std::copy(wpd.begin(), wpd.end(), wp.begin() + m * np);
+      gemm_pack_bf16x3(W + m * nplain, K, N, wq.data() + m * nq);
+    }
+  }
+  void *dB = nullptr, *dBp = nullptr, *dBq = nullptr;
+  auto cleanup = [&]() {
+    (void)hipFree(dB);
+    (void)hipFree(dBp);
+    (void)hipFree(dBq);
+  };
+  if (hipMalloc(&dB, nw * nplain * sizeof(T)) != hipSuccess || hipMemcpy(dB, W, nw * nplain * sizeof(T), hipMemcpyHostToDevice) != hipSuccess ||
+      (f32 && (hipMalloc(&dBp, nw * np * sizeof(T)) != hipSuccess || hipMemcpy(dBp, wp.data(), nw * np * sizeof(T), hipMemcpyHostToDevice) != hipSuccess ||
+               hipMalloc(&dBq, nw * nq * 4) != hipSuccess || hipMemcpy(dBq, wq.data(), nw * nq * 4, hipMemcpyHostToDevice) != hipSuccess))) {
+    cleanup();
+    return fail(AA_ERR_HIP, "aa_debug_gemm: weight upload failed");
+  }
+  g.B = dB;
+  g.Bp = dBp;
+  g.Bq = dBq;
+  g.b_bs = int64_t(nplain);
+  g.bp_bs = int64_t(np);
+  g.bq_bs = int64_t(nq);  // (4-byte words)
+  int rc = launch_gemm<T>(g, s);
+  if (rc == AA_OK) *form = int32_t(gemm_form<T>(g));
+  if (rc == AA_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(AA_ERR_HIP, "aa_debug_gemm: kernel failed");
+  cleanup();
+  return rc;
+}
+}  // namespace
+
+extern "C" int aa_debug_gemm(const aa_gemm_desc* desc, int32_t* form, aa_stream stream) {
+  AA_REQUIRE(desc && form, "aa_debug_gemm: null argument");
+  const aa_gemm_desc& d = *desc;
+  AA_REQUIRE(d.dtype == AA_F32 || d.dtype == AA_F64, "aa_debug_gemm: dtype");
+  AA_REQUIRE(d.M >= 0 && d.K > 0 && d.N > 0 && d.a_count >= 1 && d.a_count <= 3 && d.c_count >= 1 && d.c_count <= 3,
+             "aa_debug_gemm: bad shape or segment count");
+  AA_REQUIRE(d.weights && d.num_weights >= 1 && d.num_weights <= 16, "aa_debug_gemm: 1 to 16 host weight matrices");
+  AA_REQUIRE(d.batch >= 0 && d.batch <= 16, "aa_debug_gemm: batch");
+  AA_REQUIRE(d.batch > 1 || d.bsel4 == 0, "aa_debug_gemm: bsel4 selects weights for batched launches only");
+  for (int b = 0; b < (d.batch > 1 ? d.batch : 1); ++b)
+    AA_REQUIRE(int((d.bsel4 >> (4 * b)) & 15ull) < d.num_weights, "aa_debug_gemm: bsel4 selects a missing weight matrix");
+  for (int b = d.batch > 1 ? d.batch : 1; b < 16; ++b) AA_REQUIRE(((d.bsel4 >> (4 * b)) & 15ull) == 0, "aa_debug_gemm: bsel4 beyond the batch");
+  *form = AA_GEMM_FORM_NONE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return d.dtype == AA_F32 ? debug_gemm<float>(d, form, s) : debug_gemm<double>(d, form, s);
 }

@@ -454,6 +454,80 @@ void aa_model_file_close(aa_model_file* file);
 int aa_debug_gemm_f32(int kernel, int64_t M, int K, int N, const float* A_dev, const float* W_host, float* C_dev,
                       aa_stream stream);
 
+/*    aa_debug_gemm: one linear layer through the full argument surface of the scalar-MLP GEMM (aa_gemm.hip, launch_gemm):
+ *        C_seg (=|+=) ((act(A_segs) @ W_sel) [+ add_seg]) [* act'(z_seg)]
+ *    A is split over 1..3 column segments (K = sum of their widths), C / z / add over 1..3 (N = sum; z and add segment
+ *    widths equal C's).  Every pointer is device memory of `dtype`; ld is the row stride in elements.  A C segment with a
+ *    NULL pointer is computed but not stored.  act_a: activate A on load, on columns [act_lo, act_hi) (multiples of 32)
+ *    or on every column (act_hi == 0); act_kind: 0 silu, 1 mish, 2 gelu, 3 none.
+ *    batch > 1 (<= 16, no z / add): problem b reads A + b a_bs, writes C + b c_bs (elements) and multiplies by weight
+ *    matrix number (bsel4 >> 4 b) & 15.  weights: num_weights row-major K x N HOST matrices of `dtype`, back to back,
+ *    packed here with the model's own host packers.  The option fields are the aa_plan_options pass-throughs.
+ *    *form receives the aa_gemm_form that ran.  Allocates temporaries and synchronises the stream: test use only. */
+typedef enum {
+  AA_GEMM_FORM_NONE = 0, /* M == 0: nothing launched */
+  /* fp64 */
+  AA_GEMM_F64_VALU = 1,
+  AA_GEMM_F64_MFMA = 2,               /* plain f64 MFMA kernel (unaligned or odd-width operands) */
+  AA_GEMM_F64_PIPE_GRID = 3,          /* pipelined f64 MFMA kernel on a 2-D grid */
+  AA_GEMM_F64_PIPE_LOOP = 4,          /* the same, one workgroup per row tile looping over the column tiles */
+  AA_GEMM_F64_ROWS_ACC = 5,           /* row-resident, output held in accumulators (N <= 128) */
+  AA_GEMM_F64_ROWS_OPND = 6,          /* row-resident, operand rows held in registers (K <= 128) */
+  AA_GEMM_F64_ROWS_ACC_BATCHED = 7,   /* the two above as one launch over a batch of problems */
+  AA_GEMM_F64_ROWS_OPND_BATCHED = 8,
+  AA_GEMM_F64_VALU_EACH = 9,          /* a batch on a kernel without a batched form: one launch per problem */
+  AA_GEMM_F64_MFMA_EACH = 10,
+  AA_GEMM_F64_PIPE_GRID_EACH = 11,
+  AA_GEMM_F64_PIPE_LOOP_EACH = 12,
+  /* fp32 (K2 / K4: K <= 64 / 128, operand fragments held in registers; KS: operand chunks streamed) */
+  AA_GEMM_F32_VALU = 13,
+  AA_GEMM_F32_MFMA_V1 = 14,           /* fp32-input MFMA, LDS-staged operands */
+  AA_GEMM_F32_V3_K2 = 15,             /* fp32-input MFMA, operands straight from memory */
+  AA_GEMM_F32_V3_K4 = 16,
+  AA_GEMM_F32_V3_KS = 17,
+  AA_GEMM_F32_BF16X3_K2 = 18,         /* split-precision bf16 MFMA, direct epilogue */
+  AA_GEMM_F32_BF16X3_K4 = 19,
+  AA_GEMM_F32_BF16X3_KS = 20,
+  AA_GEMM_F32_BF16X3_LDS_K2 = 21,     /* split-precision bf16 MFMA, epilogue through LDS */
+  AA_GEMM_F32_BF16X3_LDS_K4 = 22,
+  AA_GEMM_F32_BF16X3_LDS_KS = 23,
+  AA_GEMM_F32_BF16X3_BATCHED_K2 = 24, /* direct-epilogue bf16x3 as one launch over a batch of problems */
+  AA_GEMM_F32_BF16X3_BATCHED_K4 = 25,
+  AA_GEMM_F32_BF16X3_BATCHED_KS = 26,
+  AA_GEMM_F32_VALU_EACH = 27,         /* a batch on a kernel without a batched form: one launch per problem */
+  AA_GEMM_F32_MFMA_V1_EACH = 28,
+  AA_GEMM_F32_V3_EACH = 29,
+  AA_GEMM_F32_BF16X3_LDS_EACH = 30
+} aa_gemm_form;
+
+typedef struct {
+  void* p;    /* device pointer to element (0, 0) of the segment */
+  int32_t ld; /* row stride, elements */
+  int32_t n;  /* columns */
+} aa_gemm_seg;
+
+typedef struct {
+  int32_t dtype; /* aa_dtype */
+  int32_t K, N;
+  int64_t M;
+  int32_t a_count, c_count; /* 1..3 each */
+  aa_gemm_seg a[3];
+  aa_gemm_seg c[3];
+  int32_t c_accum[3];       /* per C segment: 1 -> += */
+  int32_t has_z, has_add;   /* z / add split like C */
+  aa_gemm_seg z[3];
+  aa_gemm_seg add[3];
+  int32_t act_a, act_lo, act_hi, act_kind;
+  int32_t batch;            /* 0 or 1: one problem */
+  int64_t a_bs, c_bs;
+  uint64_t bsel4;
+  int32_t num_weights;      /* 1..16 */
+  const void* weights;      /* HOST [num_weights][K][N] of dtype */
+  int32_t force_kernel;     /* 0 automatic, 1 native fp32-input MFMA, 3 VALU */
+  int32_t v1, lds_epilogue, f64_rows, f64_column_loop; /* aa_plan_options.gemm_v1, gemm_lds_epilogue, f64_rows, f64_column_loop */
+} aa_gemm_desc;
+int aa_debug_gemm(const aa_gemm_desc* desc, int32_t* form, aa_stream stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
