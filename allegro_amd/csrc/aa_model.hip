@@ -191,6 +191,154 @@ extern "C" int aa_tp_backward_weights(const aa_tp_plan* plan, int64_t E, int64_t
 }
 
 // ------------------------------------------------------------------------------------------------
+// model pipeline: which kernels a plan runs, decided once at plan time (choose_pipeline)
+// ------------------------------------------------------------------------------------------------
+// Tensor-product path, least to most specialised.  From Moments on the env weights go through per-atom moments: no [E,R*u]
+// env tensors (TpMomArgs / TpOpArgs).
+enum class TpPath {
+  General,    // per-edge kernels on LDS coupling tables, reference layouts
+  Spec,       // per-edge kernels with compile-time Clebsch-Gordan tables, channel-minor internal layouts
+  SpecChain,  // ... with the 2-layer chain kernel for layer 1 (no [E,u,D] tensors in HBM)
+  Moments,    // 2-layer moments kernels (u = 64)
+  Operator,   // per-atom operator kernels (aa_tp_op.hip; any L <= 3, u = 64 m)
+};
+enum class LinearPath {
+  Single,  // one launch per linear layer
+  Slot,    // single layers on output-folded weights, reverse by dense-net slot (aa_model_plan::s_*)
+  Chains,  // MLP chains fused into gemm_chain_bf16x3_kernel (hidden layers stay in registers)
+};
+
+struct ModelPipeline {
+  // widened sizes: the model's own where nothing was padded (aa_model_plan::u_raw / hid_raw keep those)
+  int num_tensor, embed_width, latent_width, readout_width;
+  int spec_sig[AA_MAX_LAYERS];  // generated-signature id per layer (at the widened channel count), or -1
+  TpPath tp;
+  int chain_pair;     // >= 0: pair id of a 2-layer stack on the chain kernels (SpecChain, Moments; an Operator plan keeps the id)
+  int tp_op;          // >= 0: signature chain of the operator kernels (exactly the Operator plans)
+  LinearPath linear;
+  bool op_proj;       // Operator: the env projections as batched linear-layer launches (TpOpArgs::proj_gemm)
+  bool two_body_table;       // blob carries [T*T][8][S0] type_embed(c | pair) * basis_linear[n][c] (spline models: the spline weights)
+  bool embed_fused;          // reverse pass: d(two-body embedding) [E,S0] never materialised, the last reverse chain contracts it
+                             // back to the 8 basis functions in its epilogue (embrev_out in aa_common.h)
+  // weight folds the blob carries (aa_common.h; a fold that is off keeps its blob offsets at 0)
+  bool fold_embed_table;     // the two-body table times the first scalar_embed_mlp layer
+  bool fold_embed_output;    // W1 @ G0, W1 @ Wenv0: the output layer of scalar_embed_mlp folded into its consumers
+  bool fold_latent_outputs;  // first layers of latent 1 / edge_readout / the readout-reverse chain with the latent output layers folded
+  bool fold_lat0_reverse;    // ... and the chain's second layer with Wout_0^T folded into the lat0 columns (d a_0 instead of d lat0)
+  bool fused_fwd;            // the whole forward as ONE per-atom-tile kernel when the graph allows (aa_fused.hip)
+  bool fused_wide;           // ... its one-tile pass on the eight-wave form (two waves per SIMD, aa_fused8.hip)
+
+  bool channel_minor() const { return tp != TpPath::General; }
+  bool env_moments() const { return tp == TpPath::Moments || tp == TpPath::Operator; }
+  bool chains() const { return linear == LinearPath::Chains; }  // (with them: the merged readout-reverse chain, o_b3{a,b,c}_q)
+  bool slot() const { return linear == LinearPath::Slot; }
+};
+
+// The whole plan-time decision, from the caller's configuration and options alone: no HIP call, no allocation.
+static ModelPipeline choose_pipeline(const aa_model_config& q, const aa_plan_options& opt) {
+  const int L = q.num_layers, S = q.num_scalar, T = q.num_types, B = q.num_bessels, S0 = q.embed_dim;
+  const bool f32 = q.dtype == AA_F32;
+  // every fused fast path below has SiLU built in; the other nonlinearities run the general kernels
+  const bool all_silu = q.act_kind[0] == AA_ACT_SILU && q.act_kind[1] == AA_ACT_SILU && q.act_kind[2] == AA_ACT_SILU;
+  const bool scalars_ok = all_silu && (S == 64 || S == 128) && !opt.tp_no_moments;
+
+  // ---- widened sizes ----
+  // Channel padding.  A stack whose tensor-channel count is not a multiple of 64 (16 <= u < 256) is evaluated as the
+  // next multiple-of-64 stack whose extra channels have zero weights: env_embed_linear / the env columns of first_proj and of the latent outputs / the scalar rows of
+  // the latent inputs are zero-padded at pack time (aa_model_pack_weights), so the padded channels carry exact zeros
+  // through every layer and the results are those of the narrow model -- which thereby runs the tuned 64-channel
+  // kernels (moments or per-atom operator kernels, fused chains, fused forward) instead of the per-edge ones (BASELINE config 0, u = 32: 26 launches
+  // and 0.40 ms per step on 64 atoms without, 15 launches with).  Only where the 64-channel stack takes that path: the
+  // pad-eligible stack is the moments / operator shape below without the sizes that padding itself settles.
+  const bool pad_stack = !opt.no_channel_padding && scalars_ok && (L == 2 || L == 3) && !opt.tp_generic && !opt.tp_no_chain;
+  // Hidden-width padding, same idea: a single hidden layer narrower than 64 (the reference's constructor default for
+  // edge_readout is 32, allegro_models.py:137) is zero-padded to 64 -- silu(0) = 0 and there are no biases, so the
+  // extra units stay exactly zero -- which is what lets the stack run the fused linear-layer chains.
+  auto widened = [&](int depth, int width) { return (pad_stack && depth == 1 && width >= 8 && width < 64) ? 64 : width; };
+  const int He = widened(q.embed_mlp_depth, q.embed_mlp_width), H = widened(q.latent_mlp_depth, q.latent_mlp_width),
+            Hr = widened(q.readout_mlp_depth, q.readout_mlp_width);
+  const bool latents_ok = q.latent_mlp_depth >= 1 && (H == 64 || H == 128);
+  const int u_pad = (q.num_tensor + 63) / 64 * 64;  // 16..63 -> 64 (moments / operator kernels), 65..127 -> 128, ... (operator kernels)
+  const bool pad = pad_stack && latents_ok && q.num_tensor >= 16 && q.num_tensor != u_pad && u_pad <= 256;
+  const int u = pad ? u_pad : q.num_tensor;
+  const int Dsh = (q.l_max + 1) * (q.l_max + 1);
+
+  // ---- shapes of the linear-layer paths ----
+  const bool chains_shape = f32 && S == 64 && q.embed_mlp_depth == 1 && He == 64 && q.latent_mlp_depth == 1 && H == 64 &&
+                            q.readout_mlp_depth == 1 && Hr == 64 && S0 % 32 == 0 && !opt.gemm_no_chain && !opt.gemm_fp32_mfma &&
+                            !opt.gemm_valu;
+  const bool slot_shape = !opt.no_slot_form && q.latent_mlp_depth == 1 && H == S && q.readout_mlp_depth >= 1 && q.embed_mlp_depth >= 1 &&
+                          He == S && (Hr % 16) == 0;
+
+  // ---- tensor-product path ----
+  ModelPipeline m{};
+  bool sigs_ok = !opt.tp_generic;
+  for (int l = 0; l < L; ++l) {
+    aa_tp_desc d = q.tps[l];
+    if (pad) d.mul = u;
+    m.spec_sig[l] = find_spec_sig(d);
+    sigs_ok = sigs_ok && m.spec_sig[l] >= 0;
+  }
+  // fp64 at l_max=3 does not fit the register file (256 VGPR + 256 AGPR + 1.9 KB scratch per lane, and
+  // wrong results on hardware in round 1): keep it on the general LDS-table kernels for now
+  const bool spec = sigs_ok && !(q.dtype == AA_F64 && q.l_max >= 3);
+  const int chain_pair = (spec && L == 2 && !opt.tp_no_chain) ? find_chain_pair(m.spec_sig[0], m.spec_sig[1]) : -1;
+  // moments shape: a 2-layer chain pair at u = 64 whose workgroups (last term) fit the 160 KB of LDS
+  const bool moments_ok = scalars_ok && latents_ok && chain_pair >= 0 && u == 64 &&
+                          (f32 ? 4 : 8) * 4 * Dsh * (std::max(S, H) + 64 + 64) <= 160 * 1024;
+  // operator shape: every standard stack the tuned 2-layer/u=64 kernels above do not cover (and, with
+  // tp_force_operator, those too); they need the channel-minor layouts of the specialised path but none of its kernels,
+  // so fp64 at l_max = 3 is fine here
+  const bool operator_ok = scalars_ok && latents_ok && sigs_ok && L >= 2 && L <= 3 && (u % 64) == 0 && u <= 256 && !opt.tp_no_operator;
+  // Where the 2-layer moments kernels apply but the fused chains do NOT (fp64; S or the MLP widths 128; deeper MLPs), the operator
+  // kernels -- with the slot form of the linear layers where that applies -- are the faster pipeline: measured on the C3 box
+  // (profiles/r05_v3_shape_map_c3.md against r05_v7 / r05_v8 with the operator path forced): fp32 u 64 / S 128 7.41 -> 3.96 ms,
+  // fp64 u = S = 64 4.89 -> 4.14 ms, fp64 S 128 8.80 -> 6.82 ms; fp32 S 64 with 128-wide latents is a wash (3.70 vs 3.76 ms) and
+  // keeps the moments kernels.
+  const bool prefer_op = moments_ok && !chains_shape && (slot_shape || !f32) && !opt.tp_prefer_moments;
+  const int tp_op = (operator_ok && (!moments_ok || opt.tp_force_operator || prefer_op)) ? find_op_chain(m.spec_sig, L) : -1;
+  m.tp = tp_op >= 0 ? TpPath::Operator : moments_ok ? TpPath::Moments : chain_pair >= 0 ? TpPath::SpecChain : spec ? TpPath::Spec : TpPath::General;
+  m.chain_pair = chain_pair;
+  m.tp_op = tp_op;
+  m.op_proj = tp_op >= 0 && opt.op_proj_gemm != 2;
+
+  // ---- linear-layer path, folds ----
+  const bool chains = m.env_moments() && (tp_op < 0 || u == 64) && chains_shape;
+  m.linear = chains ? LinearPath::Chains : (tp_op >= 0 && slot_shape) ? LinearPath::Slot : LinearPath::Single;
+  // two-body table [T*T][B][S0] (type embedding x basis weights): the last reverse chain contracts against it (<= 2
+  // species: its LDS copy must leave room for three workgroups per CU) and the fused forward evaluates the embedding
+  // from it (<= 3 species: 18 KB of its LDS).  Part of the blob whenever the shapes allow -- not a function of the options.
+  const bool tab_ok = chains && T <= 3 && B == 8 && S0 == 64;
+  m.two_body_table = tab_ok || q.embed_kind == 1;
+  m.embed_fused = tab_ok && T <= 2 && !opt.embed_no_fuse;
+  m.fold_embed_table = tab_ok;  // (the fold needs a hidden layer of 64 behind the embedding: what the chains have)
+  const bool chains2 = chains && L == 2;  // (chains: u = 64, S = every MLP width = 64, one hidden layer each)
+  m.fold_embed_output = chains2;
+  m.fold_latent_outputs = chains2;
+  m.fold_lat0_reverse = chains2;
+
+  // ---- fused forward ----
+  // fused per-atom-tile forward (aa_fused.hip): the standard 2-layer 64-wide fp32 stack with the
+  // two-body table in LDS; same parity tests as the staged pipeline.  With the tensor-track scalars accumulated in
+  // anchored program order (aa::anchor -- the kernel used to carry 70-350 spilled VGPRs) the 32-edge-tile form beats the
+  // staged forward at every size on MI355X: 22-24 % of the step on 64-1000 atoms (one launch instead of seven), 9 % at
+  // 4096, 4.5 % at 10 648, 0.5 % at 97 336 atoms, and it moves 2.1 instead of 7.3 KB/edge (profiles/archive/r02_v23_fused_sweep.log).
+  // aa_plan_options.fused_forward: 0 / 1 = whenever the graph allows (automatic), 3 = never (staged pipeline); A/B: 2 = also for every
+  // graph with segments <= 128, in the pure team form, 4 = the same in the mixed form.
+  // Eligible: the moments kernels of l_max 1 / 2 with every fold of the kernel's weight program packed.
+  const bool fused = m.tp == TpPath::Moments && (chain_pair == 0 || chain_pair == 1) && m.fold_embed_table && m.fold_embed_output &&
+                     m.fold_latent_outputs && opt.fused_forward != 3;
+  m.fused_fwd = fused;
+  // the two-waves-per-SIMD form (aa_fused8.hip) needs a two-body table that leaves 16.6 KB of LDS per wave (one species)
+  m.fused_wide = fused && opt.fused_narrow != 1 && fused_fwd8_lds_bytes(T, 8) <= 160 * 1024;
+  m.num_tensor = u;
+  m.embed_width = He;
+  m.latent_width = H;
+  m.readout_width = Hr;
+  return m;
+}
+
+// ------------------------------------------------------------------------------------------------
 // model plan
 // ------------------------------------------------------------------------------------------------
 struct MlpLayout {
@@ -213,8 +361,9 @@ struct GemmMatSet {
 };
 
 struct aa_model_plan {
-  aa_model_config cfg;
+  aa_model_config cfg;               // at the widened sizes of `pipe`
   aa_plan_options opt{};
+  ModelPipeline pipe{};              // what the plan runs: set by choose_pipeline in aa_model_plan_create, read everywhere else
   int D, R, W, SL1;  // SH dim, irreps, env weight numel, S*(L+1)
   std::vector<std::vector<int32_t>> keep_i32;
   std::vector<std::vector<double>> keep_f64;
@@ -226,35 +375,25 @@ struct aa_model_plan {
   MlpLayout embed, readout;          // readout: only the GEMM layers (all but the final ->1 layer)
   MlpLayout latent[AA_MAX_LAYERS];
   int ro_last_dim;                   // input dim of the final readout linear
-  int spec_sig[AA_MAX_LAYERS];       // generated-signature id per layer, or -1
-  bool use_spec;                     // all layers specialised -> channel-minor internal layouts
   int u_raw;                         // num_tensor_features of the model; cfg.num_tensor is the next multiple of 64 when the channels were padded
   int hid_raw[3];                    // hidden widths of scalar_embed_mlp / latent MLPs / edge_readout in the model (cfg holds the padded ones)
-  int chain_pair;                    // >= 0: 2-layer stack on the chain kernels (no [E,u,D] tensors in HBM)
-  bool env_mom;                      // env weights through per-atom moments: no [E,R*u] env tensors (TpMomArgs / TpOpArgs)
-  int tp_op;                         // >= 0: signature chain of the per-atom operator kernels (aa_tp_op.hip; any L <= 3, u = 64 m)
-  bool chain_gemm;                   // MLP chains fused into gemm_chain_bf16x3_kernel (hidden layers stay in registers)
-  bool fused_fwd;                    // the whole forward as ONE per-atom-tile kernel when the graph allows (aa_fused.hip)
-  bool fused_wide = false;           // ... its one-tile pass on the eight-wave form (two waves per SIMD, aa_fused8.hip)
   mutable bool taps = false;         // aa_model_plan_enable_taps: staged pipeline so that every tap is materialised
-  bool embed_fused;                  // reverse pass: d(two-body embedding) [E,S0] never materialised, the last reverse chain
-                                     // contracts it back to the 8 basis functions in its epilogue (embrev_out in aa_common.h)
-  size_t o_embtab;                   // [T*T][8][64] type_embed(c | pair) * basis_linear[n][c]
-  size_t o_embtab_h;                 // [T*T][8][64] the same table times the first scalar_embed_mlp layer (fold_embed_table), or 0
+  // blob offsets of the optional parts: positions only, 0 where the part is absent -- whether it exists is pipe's to say
+  size_t o_embtab;                   // (two_body_table) [T*T][8][64] type_embed(c | pair) * basis_linear[n][c]
+  size_t o_embtab_h;                 // (fold_embed_table) [T*T][8][64] the same table times the first scalar_embed_mlp layer
   size_t o_lat1in_fq, o_ro0_fq;      // (fold_latent_outputs, 2-layer 64-wide stacks) bf16x3 copies of the first layers of latent 1 / edge_readout with the
-                                     // latent output layers folded into their lat_l row blocks, or 0
-  size_t o_b3af_q;                   // ... and of the merged first layer of the readout-reverse chain, or 0
-  size_t o_b3bf_q;                   // ... and of its second layer with Wout_0^T folded into the lat0 columns (d a_0 instead of d lat0), or 0
-  size_t o_g0fq, o_g0tfq;            // (fold_embed_output) bf16x3 copies of W1 @ G0 [64, ng0] and of its transpose, or 0
-  size_t o_wk0f, o_wt0f;             // (fold_embed_output) W1 @ Wenv0 as [k][R][u] and [R][u][k], or 0
-  // "Slot form" of the single-layer pipeline (operator-kernel plans: C5 and every standard stack off the tuned 2-layer shape).
+                                     // latent output layers folded into their lat_l row blocks
+  size_t o_b3af_q;                   // ... and of the merged first layer of the readout-reverse chain
+  size_t o_b3bf_q;                   // (fold_lat0_reverse) ... and of its second layer with Wout_0^T folded into the lat0 columns (d a_0 instead of d lat0)
+  size_t o_g0fq, o_g0tfq;            // (fold_embed_output) bf16x3 copies of W1 @ G0 [64, ng0] and of its transpose
+  size_t o_wk0f, o_wt0f;             // (fold_embed_output) W1 @ Wenv0 as [k][R][u] and [R][u][k]
+  // "Slot form" of the single-layer pipeline (LinearPath::Slot; operator-kernel plans: C5 and every standard stack off the tuned 2-layer shape).
   // The same algebra as fold_embed_output / fold_latent_outputs (aa_common.h), for any depth: the output layer of scalar_embed_mlp and of every latent MLP is
   // folded into its consumers at pack time, so slot l + 1 of the dense-net buffer holds the latent's hidden PRE-ACTIVATION z_l
   // (consumers activate those columns on load, GemmArgs::act_lo / act_hi) and the layers "a -> lat_l" do not exist.  The reverse
   // is evaluated BY SLOT, not by consumer: d z_l = ([d readout hidden | d z_{l+1} .. d z_{L-1}] @ stack_l + d a_l of the moments)
   // * act'(z_l) -- one K-stacked layer with 128-wide output per latent (the accumulator-resident kernel's shape, every slot
   // written once) instead of wide accumulate-into-the-dense-net layers.
-  bool slot_form;
   GemmMat s_g0f, s_g0ft;             //   W_last(embed) @ G0 [He, ng0] and its transpose
   GemmMat s_in[AA_MAX_LAYERS];       //   first layer of latent l with the row blocks of earlier latents folded  [S (l+1) + u, H]
   GemmMat s_ro0;                     //   first readout layer, folded                                             [SL1, Hr]
@@ -262,9 +401,8 @@ struct aa_model_plan {
   GemmMat s_rstb;                    //   reverse stack of slot 0 (two-body): rows [readout | latent 0 .. L-1]      [Hr + S L, S]
   GemmMat s_sct[AA_MAX_LAYERS];      //   d z_l -> d (tensor scalars of layer l)                                   [H, u]
   size_t o_s_wk0, o_s_wt0;           //   W_last(embed) @ Wenv0 as [k][R][u] and [R][u][k]
-  // operator-kernel plans: the env projections as batched linear-layer launches (TpOpArgs::proj_gemm) -- per layer the R matrices
+  // operator-kernel plans (pipe.op_proj): the env projections as batched linear-layer launches (TpOpArgs::proj_gemm) -- per layer the R matrices
   // f Wenv_l[:, r, :] [ka, u] and their transposes [u, ka]; layer 0 also behind the output layer of scalar_embed_mlp (slot form)
-  bool op_proj;
   GemmMatSet s_pr[AA_MAX_LAYERS], s_prt[AA_MAX_LAYERS], s_pr0f, s_prt0f;
   int ng0;                           // output width of the fused first-stage GEMM
   size_t o_wk[AA_MAX_LAYERS], o_wt[AA_MAX_LAYERS];  // Wenv of layer l as [ka][R][u] and [R][u][ka]
@@ -320,43 +458,7 @@ static std::vector<int> mlp_dims(int in, int depth, int width, int out) {
   return d;
 }
 
-extern "C" int aa_model_plan_create(const aa_model_config* cfg, aa_model_plan** out) {
-  return aa_model_plan_create_with_options(cfg, nullptr, out);
-}
-
-extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, const aa_plan_options* options, aa_model_plan** out) {
-  AA_REQUIRE(cfg_in && out, "aa_model_plan_create: null argument");
-  const aa_plan_options opt = options ? *options : aa_plan_options{};
-  // Channel padding.  A stack whose tensor-channel count is not a multiple of 64 (16 <= u < 256) is evaluated as the
-  // next multiple-of-64 stack whose extra channels have zero weights: env_embed_linear / the env columns of first_proj and of the latent outputs / the scalar rows of
-  // the latent inputs are zero-padded at pack time (aa_model_pack_weights), so the padded channels carry exact zeros
-  // through every layer and the results are those of the narrow model -- which thereby runs the tuned 64-channel
-  // kernels (moments or per-atom operator kernels, fused chains, fused forward) instead of the per-edge ones (BASELINE config 0, u = 32: 26 launches
-  // and 0.40 ms per step on 64 atoms without, 15 launches with).  Only where the 64-channel stack takes that path.
-  aa_model_config cfg_local = *cfg_in;
-  const int u_raw = cfg_in->num_tensor;
-  {
-    const aa_model_config& q = *cfg_in;
-    const bool silu = q.act_kind[0] == AA_ACT_SILU && q.act_kind[1] == AA_ACT_SILU && q.act_kind[2] == AA_ACT_SILU;
-    const int u_pad = (u_raw + 63) / 64 * 64;  // 16..63 -> 64 (moments / operator kernels), 65..127 -> 128, ... (operator kernels)
-    const bool pad = !opt.no_channel_padding && u_raw >= 16 && u_raw != u_pad && u_pad <= 256 && silu && (q.num_layers == 2 || q.num_layers == 3) &&
-                     (q.num_scalar == 64 || q.num_scalar == 128) && q.latent_mlp_depth >= 1 &&
-                     (q.latent_mlp_width == 64 || q.latent_mlp_width == 128 || (q.latent_mlp_depth == 1 && q.latent_mlp_width >= 8 && q.latent_mlp_width < 64)) &&
-                     !opt.tp_generic && !opt.tp_no_chain && !opt.tp_no_moments;
-    if (pad) {
-      cfg_local.num_tensor = u_pad;
-      for (int l = 0; l < q.num_layers && l < AA_MAX_LAYERS; ++l) cfg_local.tps[l].mul = u_pad;
-    }
-    // Hidden-width padding, same idea: a single hidden layer narrower than 64 (the reference's constructor default for
-    // edge_readout is 32, allegro_models.py:137) is zero-padded to 64 -- silu(0) = 0 and there are no biases, so the
-    // extra units stay exactly zero -- which is what lets the stack run the fused linear-layer chains.
-    const bool hid = !opt.no_channel_padding && silu && (q.num_layers == 2 || q.num_layers == 3) && (q.num_scalar == 64 || q.num_scalar == 128) &&
-                     !opt.tp_generic && !opt.tp_no_chain && !opt.tp_no_moments;
-    if (hid && q.embed_mlp_depth == 1 && q.embed_mlp_width >= 8 && q.embed_mlp_width < 64) cfg_local.embed_mlp_width = 64;
-    if (hid && q.latent_mlp_depth == 1 && q.latent_mlp_width >= 8 && q.latent_mlp_width < 64) cfg_local.latent_mlp_width = 64;
-    if (hid && q.readout_mlp_depth == 1 && q.readout_mlp_width >= 8 && q.readout_mlp_width < 64) cfg_local.readout_mlp_width = 64;
-  }
-  const aa_model_config* cfg = &cfg_local;
+static int validate_config(const aa_model_config* cfg) {
   AA_REQUIRE(cfg->dtype == AA_F32 || cfg->dtype == AA_F64, "model: bad dtype");
   AA_REQUIRE(cfg->l_max >= 1 && cfg->l_max <= 3, "model: l_max must be 1..3");
   for (int i = 0; i < 3; ++i) AA_REQUIRE(cfg->act_kind[i] >= AA_ACT_SILU && cfg->act_kind[i] <= AA_ACT_NONE, "model: unknown nonlinearity");
@@ -366,13 +468,35 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
              "model: MLP too deep");
   AA_REQUIRE(cfg->num_types > 0 && cfg->num_bessels > 0 && cfg->num_bessels <= 16 && cfg->embed_dim % 2 == 0,
              "model: bad embedding sizes");
+  AA_REQUIRE(cfg->embed_kind == 0 || (cfg->embed_kind == 1 && cfg->spline_span >= 0 && cfg->spline_span <= cfg->num_bessels),
+             "model: embed_kind must be 0 (Bessel) or 1 (spline, 0 <= span <= num_splines)");
+  return AA_OK;
+}
+
+extern "C" int aa_model_plan_create(const aa_model_config* cfg, aa_model_plan** out) {
+  return aa_model_plan_create_with_options(cfg, nullptr, out);
+}
+
+// validate -> choose_pipeline -> lay out the weight blob
+extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, const aa_plan_options* options, aa_model_plan** out) {
+  AA_REQUIRE(cfg_in && out, "aa_model_plan_create: null argument");
+  if (int rc = validate_config(cfg_in)) return rc;
   aa_model_plan* p = new aa_model_plan();
-  p->cfg = *cfg;
-  p->u_raw = u_raw;
+  p->opt = options ? *options : aa_plan_options{};
+  p->pipe = choose_pipeline(*cfg_in, p->opt);
+  const ModelPipeline& pipe = p->pipe;
+  p->u_raw = cfg_in->num_tensor;
   p->hid_raw[0] = cfg_in->embed_mlp_width;
   p->hid_raw[1] = cfg_in->latent_mlp_width;
   p->hid_raw[2] = cfg_in->readout_mlp_width;
-  p->opt = opt;
+  p->cfg = *cfg_in;  // ... at the widened sizes
+  p->cfg.num_tensor = pipe.num_tensor;
+  p->cfg.embed_mlp_width = pipe.embed_width;
+  p->cfg.latent_mlp_width = pipe.latent_width;
+  p->cfg.readout_mlp_width = pipe.readout_width;
+  if (pipe.num_tensor != p->u_raw)
+    for (int l = 0; l < p->cfg.num_layers; ++l) p->cfg.tps[l].mul = pipe.num_tensor;
+  const aa_model_config* cfg = &p->cfg;
   const int L = cfg->num_layers, S = cfg->num_scalar, u = cfg->num_tensor;
   p->R = cfg->l_max + 1;
   p->D = p->R * p->R;
@@ -391,53 +515,9 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
     if (!ok) return bail(fail(AA_ERR_INVALID, "model: tensor-product layer dims are inconsistent"));
     int rc = build_tp_layer(d, &p->layers[l], &p->owned);
     if (rc) return bail(rc);
-    p->spec_sig[l] = find_spec_sig(d);
     // the plan must not keep pointers into the caller's descriptor arrays
     p->cfg.tps[l].nz_i = p->cfg.tps[l].nz_j = p->cfg.tps[l].nz_k = p->cfg.tps[l].nz_path = nullptr;
     p->cfg.tps[l].nz_val = nullptr;
-  }
-  {
-    p->use_spec = !opt.tp_generic;
-    for (int l = 0; l < L; ++l) p->use_spec = p->use_spec && p->spec_sig[l] >= 0;
-    // fp64 at l_max=3 does not fit the register file (256 VGPR + 256 AGPR + 1.9 KB scratch per lane, and
-    // wrong results on hardware in round 1): keep it on the general LDS-table kernels for now
-    if (cfg->dtype == AA_F64 && cfg->l_max >= 3) p->use_spec = false;
-    p->chain_pair = -1;
-    if (p->use_spec && L == 2 && !opt.tp_no_chain) p->chain_pair = find_chain_pair(p->spec_sig[0], p->spec_sig[1]);
-    const int Dsh = (cfg->l_max + 1) * (cfg->l_max + 1);
-    // every fused fast path below has SiLU built in; the other nonlinearities run the general kernels
-    const bool all_silu = cfg->act_kind[0] == AA_ACT_SILU && cfg->act_kind[1] == AA_ACT_SILU && cfg->act_kind[2] == AA_ACT_SILU;
-    p->env_mom = all_silu && p->chain_pair >= 0 && u == 64 && (S == 64 || S == 128) && cfg->latent_mlp_depth >= 1 &&
-                 (cfg->latent_mlp_width == 64 || cfg->latent_mlp_width == 128) &&
-                 (cfg->dtype == AA_F32 ? 4 : 8) * 4 * Dsh * (std::max(S, cfg->latent_mlp_width) + 64 + 64) <= 160 * 1024 &&
-                 !opt.tp_no_moments;
-    // per-atom operator kernels: every standard stack the tuned 2-layer/u=64 kernels above do not cover (and, with
-    // AA_TP_OP=1, those too); they need the channel-minor layouts of the specialised path but none of its kernels,
-    // so fp64 at l_max = 3 is fine here
-    p->tp_op = -1;
-    bool sigs_ok = !opt.tp_generic;
-    for (int l = 0; l < L; ++l) sigs_ok = sigs_ok && p->spec_sig[l] >= 0;
-    // Where the 2-layer moments kernels apply but the fused chains do NOT (fp64; S or the MLP widths 128; deeper MLPs), the operator
-    // kernels -- with the slot form of the linear layers where that applies -- are the faster pipeline: measured on the C3 box
-    // (profiles/r05_v3_shape_map_c3.md against r05_v7 / r05_v8 with the operator path forced): fp32 u 64 / S 128 7.41 -> 3.96 ms,
-    // fp64 u = S = 64 4.89 -> 4.14 ms, fp64 S 128 8.80 -> 6.82 ms; fp32 S 64 with 128-wide latents is a wash (3.70 vs 3.76 ms) and
-    // keeps the moments kernels.
-    const bool would_chain = cfg->dtype == AA_F32 && S == 64 && cfg->embed_mlp_depth == 1 && cfg->embed_mlp_width == 64 && cfg->latent_mlp_depth == 1 &&
-                             cfg->latent_mlp_width == 64 && cfg->readout_mlp_depth == 1 && cfg->readout_mlp_width == 64 && cfg->embed_dim % 32 == 0 &&
-                             !opt.gemm_no_chain && !opt.gemm_fp32_mfma && !opt.gemm_valu;
-    const bool would_slot = !opt.no_slot_form && cfg->latent_mlp_depth == 1 && cfg->latent_mlp_width == S && cfg->readout_mlp_depth >= 1 &&
-                            cfg->embed_mlp_depth >= 1 && cfg->embed_mlp_width == S && (cfg->readout_mlp_width % 16) == 0;
-    const bool prefer_op = p->env_mom && !would_chain && (would_slot || cfg->dtype == AA_F64) && !opt.tp_prefer_moments;
-    if (all_silu && sigs_ok && L >= 2 && L <= 3 && (u % 64) == 0 && u <= 256 && (S == 64 || S == 128) && cfg->latent_mlp_depth >= 1 &&
-        (cfg->latent_mlp_width == 64 || cfg->latent_mlp_width == 128) && !opt.tp_no_moments && !opt.tp_no_operator &&
-        (!p->env_mom || opt.tp_force_operator || prefer_op)) {
-      const int chain = find_op_chain(p->spec_sig, L);
-      if (chain >= 0) {
-        p->tp_op = chain;
-        p->env_mom = true;
-        p->use_spec = true;
-      }
-    }
   }
   // weight blob layout
   size_t o = 0;
@@ -452,8 +532,6 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
   p->o_cemb = take(size_t(T) * S0 / 2);
   p->o_nemb = take(size_t(T) * S0 / 2);
   p->o_basis = take(size_t(B) * S0);
-  AA_REQUIRE(cfg->embed_kind == 0 || (cfg->embed_kind == 1 && cfg->spline_span >= 0 && cfg->spline_span <= B),
-             "model: embed_kind must be 0 (Bessel) or 1 (spline, 0 <= span <= num_splines)");
   auto lay = [&](MlpLayout& m, const std::vector<int>& dims, int nlayers) {
     m.dims = dims;
     for (int i = 0; i < nlayers; ++i) {
@@ -466,20 +544,14 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
     }
   };
   lay(p->embed, mlp_dims(S0, cfg->embed_mlp_depth, cfg->embed_mlp_width, S), cfg->embed_mlp_depth + 1);
-  {
-    p->chain_gemm = p->env_mom && (p->tp_op < 0 || u == 64) && cfg->dtype == AA_F32 && S == 64 && cfg->embed_mlp_depth == 1 &&
-                    cfg->embed_mlp_width == 64 && cfg->latent_mlp_depth == 1 && cfg->latent_mlp_width == 64 &&
-                    cfg->readout_mlp_depth == 1 && cfg->readout_mlp_width == 64 && cfg->embed_dim % 32 == 0 &&
-                    !opt.gemm_no_chain && !opt.gemm_fp32_mfma && !opt.gemm_valu;
-  }
-  p->ng0 = p->env_mom ? S + p->W : S + 2 * p->W;
+  p->ng0 = pipe.env_moments() ? S + p->W : S + 2 * p->W;
   p->o_g0 = take(size_t(S) * p->ng0);
   p->o_g0t = take(size_t(S) * p->ng0);
   p->o_g0p = take(gemm_packed_elems(S, p->ng0));
   p->o_g0tp = take(gemm_packed_elems(p->ng0, S));
   p->o_g0q = take(gemm_bf16x3_words(S, p->ng0));
   p->o_g0tq = take(gemm_bf16x3_words(p->ng0, S));
-  if (p->env_mom) {
+  if (pipe.env_moments()) {
     for (int l = 0; l < L; ++l) {
       const size_t ka = l == 0 ? S : cfg->latent_mlp_width;
       p->o_wk[l] = take(ka * p->W);
@@ -487,7 +559,7 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
     }
   }
   for (int l = 0; l < L; ++l) {
-    int in = S * (l + 1) + u, outd = S + ((l < L - 1 && !p->env_mom) ? p->W : 0);
+    int in = S * (l + 1) + u, outd = S + ((l < L - 1 && !pipe.env_moments()) ? p->W : 0);
     lay(p->latent[l], mlp_dims(in, cfg->latent_mlp_depth, cfg->latent_mlp_width, outd), cfg->latent_mlp_depth + 1);
     p->o_tpw[l] = take(size_t(cfg->tps[l].coupling ? u : 1) * cfg->tps[l].num_paths);
   }
@@ -500,29 +572,21 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
   p->o_b3a_q = p->o_b3b_q = p->o_b3c_q = 0;
   p->o_lat1in_fq = p->o_ro0_fq = p->o_b3af_q = p->o_b3bf_q = 0;
   p->o_g0fq = p->o_g0tfq = p->o_wk0f = p->o_wt0f = 0;
-  if (p->chain_gemm && p->env_mom && L == 2 && u == 64) {  // (fold_embed_output)
+  if (pipe.fold_embed_output) {
     p->o_g0fq = take(gemm_bf16x3_words(64, p->ng0));
     p->o_g0tfq = take(gemm_bf16x3_words(p->ng0, 64));
     p->o_wk0f = take(size_t(64) * p->W);
     p->o_wt0f = take(size_t(64) * p->W);
   }
-  if (p->chain_gemm && L == 2 && u == 64) {  // (fold_latent_outputs; chain_gemm: S = every MLP width = 64, one hidden layer each)
+  if (pipe.fold_latent_outputs) {  // (S = u = every MLP width = 64, one hidden layer each, L = 2)
     p->o_lat1in_fq = take(gemm_bf16x3_words(2 * S + u, 64));
     p->o_ro0_fq = take(gemm_bf16x3_words(3 * S, 64));
     p->o_b3af_q = take(gemm_bf16x3_words(64, 64));
-    p->o_b3bf_q = take(gemm_bf16x3_words(128, S * L));  // (fold_lat0_reverse)
+    p->o_b3bf_q = pipe.fold_lat0_reverse ? take(gemm_bf16x3_words(128, S * L)) : 0;
   }
-  {
-    // two-body table [T*T][B][S0] (type embedding x basis weights): the last reverse chain contracts against it (<= 2
-    // species: its LDS copy must leave room for three workgroups per CU) and the fused forward evaluates the embedding
-    // from it (<= 3 species: 18 KB of its LDS).  Part of the blob whenever the shapes allow -- not a function of the options.
-    const bool tab_ok = p->chain_gemm && T <= 3 && B == 8 && S0 == 64;
-    p->embed_fused = tab_ok && T <= 2 && !opt.embed_no_fuse;
-    p->o_embtab = (tab_ok || cfg->embed_kind == 1) ? take(size_t(T) * T * B * S0) : 0;
-    // (the fold needs a hidden layer of 64 behind the embedding: what the chains / the fused forward require anyway)
-    p->o_embtab_h = (tab_ok && cfg->embed_mlp_depth >= 1 && p->embed.dims.size() >= 2 && p->embed.dims[1] == 64) ? take(size_t(T) * T * B * 64) : 0;
-  }
-  if (p->chain_gemm) {
+  p->o_embtab = pipe.two_body_table ? take(size_t(T) * T * B * S0) : 0;
+  p->o_embtab_h = pipe.fold_embed_table ? take(size_t(T) * T * B * 64) : 0;
+  if (pipe.chains()) {
     // merged reverse chain "readout' o latent_{L-1}'" (see Runner::backward): the readout-reverse columns that feed
     // the last latent, and [readout-reverse columns of the earlier features (zero-padded) ; latent-reverse] stacked
     p->o_b3a_q = take(gemm_bf16x3_words(64, S));
@@ -530,11 +594,9 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
     p->o_b3c_q = take(gemm_bf16x3_words(64, u));
   }
   {
-    const int De = cfg->embed_mlp_depth, Hr = cfg->readout_mlp_width, H = cfg->latent_mlp_width;
-    p->slot_form = !opt.no_slot_form && !p->chain_gemm && p->tp_op >= 0 && p->env_mom && cfg->latent_mlp_depth == 1 && H == S &&
-                   cfg->readout_mlp_depth >= 1 && De >= 1 && cfg->embed_mlp_width == S && (Hr % 16) == 0;
+    const int Hr = cfg->readout_mlp_width, H = cfg->latent_mlp_width;
     p->o_s_wk0 = p->o_s_wt0 = 0;
-    if (p->slot_form) {
+    if (pipe.slot()) {
       auto mat = [&](int K, int N) {
         GemmMat m;
         m.K = K;
@@ -557,8 +619,7 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
       p->o_s_wt0 = take(size_t(S) * p->W);
     }
   }
-  p->op_proj = p->tp_op >= 0 && opt.op_proj_gemm != 2;
-  if (p->op_proj) {
+  if (pipe.op_proj) {
     auto mset = [&](int K, int N, int count) {
       GemmMatSet m;
       m.K = K;
@@ -578,7 +639,7 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
       p->s_pr[l] = mset(ka, u, p->R);
       p->s_prt[l] = mset(u, ka, p->R);
     }
-    if (p->slot_form) {
+    if (pipe.slot()) {
       p->s_pr0f = mset(S, u, p->R);
       p->s_prt0f = mset(u, S, p->R);
     }
@@ -586,21 +647,6 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
   p->o_scales = take(T);
   p->o_shifts = take(T);
   p->n_elems = o;
-  {
-    // fused per-atom-tile forward (aa_fused.hip): the standard 2-layer 64-wide fp32 stack with the
-    // two-body table in LDS; same parity tests as the staged pipeline.  With the tensor-track scalars accumulated in
-    // anchored program order (aa::anchor -- the kernel used to carry 70-350 spilled VGPRs) the 32-edge-tile form beats the
-    // staged forward at every size on MI355X: 22-24 % of the step on 64-1000 atoms (one launch instead of seven), 9 % at
-    // 4096, 4.5 % at 10 648, 0.5 % at 97 336 atoms, and it moves 2.1 instead of 7.3 KB/edge (profiles/archive/r02_v23_fused_sweep.log).
-    // aa_plan_options.fused_forward: 0 / 1 = whenever the graph allows (automatic), 3 = never (staged pipeline); A/B: 2 = also for every
-    // graph with segments <= 128, in the pure team form, 4 = the same in the mixed form.
-    const bool eligible = p->chain_gemm && p->env_mom && p->tp_op < 0 && (p->chain_pair == 0 || p->chain_pair == 1) && L == 2 &&
-                          u == 64 && S == 64 && T <= 3 && B == 8 && S0 == 64 && p->o_embtab != 0 && p->o_embtab_h != 0 && p->o_lat1in_fq != 0 &&
-                          p->o_g0fq != 0;
-    p->fused_fwd = eligible && opt.fused_forward != 3;
-    // the two-waves-per-SIMD form (aa_fused8.hip) needs a two-body table that leaves 16.6 KB of LDS per wave (one species)
-    p->fused_wide = p->fused_fwd && opt.fused_narrow != 1 && fused_fwd8_lds_bytes(cfg->num_types, 8) <= 160 * 1024;
-  }
   {
     void* st = nullptr;
     if (hipHostMalloc(&st, 64, hipHostMallocDefault) != hipSuccess || !st) {
@@ -616,7 +662,8 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
 
 extern "C" int aa_model_plan_describe(const aa_model_plan* p, char* buf, size_t n) {
   AA_REQUIRE(p && buf && n > 0, "aa_model_plan_describe: null argument");
-  const bool fused = p->fused_fwd;
+  const ModelPipeline& m = p->pipe;
+  const bool fused = m.fused_fwd;
   // MFMA steps (one step = a 64-feature tile pair x a 32-deep chunk = 24 bf16 MFMAs per 32-edge tile) of the fused forward: executed
   // (after the folds) vs the step-equivalents of the reference's linear layers (what `roofline.achieved` prices)
   const int R = p->R;
@@ -626,11 +673,11 @@ extern "C" int aa_model_plan_describe(const aa_model_plan* p, char* buf, size_t 
                          "{\"fused_forward\": %s, \"fold_embed_table\": %s, \"fold_embed_output\": %s, \"fold_latent_outputs\": %s, "
                          "\"fold_lat0_reverse\": %s, \"fused_mfma_steps_executed\": %d, \"fused_mfma_steps_reference\": %d, "
                          "\"chain_gemm\": %s, \"moments\": %s, \"operator_path\": %s, \"slot_form\": %s, \"fused_wide\": %s}",
-                         fused ? "true" : "false", (fused && p->o_embtab_h) ? "true" : "false",
-                         (fused && p->o_g0fq) ? "true" : "false", (fused && p->o_lat1in_fq) ? "true" : "false",
-                         p->o_b3bf_q ? "true" : "false", exec_steps, fused ? ref_steps : 0, p->chain_gemm ? "true" : "false",
-                         p->env_mom ? "true" : "false", p->tp_op >= 0 ? "true" : "false", p->slot_form ? "true" : "false",
-                         p->fused_wide ? "true" : "false");
+                         fused ? "true" : "false", (fused && m.fold_embed_table) ? "true" : "false",
+                         (fused && m.fold_embed_output) ? "true" : "false", (fused && m.fold_latent_outputs) ? "true" : "false",
+                         m.fold_lat0_reverse ? "true" : "false", exec_steps, fused ? ref_steps : 0, m.chains() ? "true" : "false",
+                         m.env_moments() ? "true" : "false", m.tp == TpPath::Operator ? "true" : "false", m.slot() ? "true" : "false",
+                         m.fused_wide ? "true" : "false");
   return (k < 0 || size_t(k) >= n) ? fail(AA_ERR_INVALID, "aa_model_plan_describe: buffer too small") : k;
 }
 
@@ -704,17 +751,17 @@ extern "C" uint64_t aa_model_plan_layout_hash(const aa_model_plan* p) {
   const aa_model_config& c = p->cfg;
   for (uint64_t v : {uint64_t(c.dtype), uint64_t(c.num_types), uint64_t(c.num_bessels), uint64_t(c.l_max), uint64_t(c.num_layers),
                      uint64_t(c.num_scalar), uint64_t(c.num_tensor), uint64_t(c.embed_dim), uint64_t(c.embed_mlp_width),
-                     uint64_t(c.latent_mlp_width), uint64_t(c.readout_mlp_width), uint64_t(p->u_raw), uint64_t(p->use_spec),
-                     uint64_t(p->env_mom), uint64_t(p->chain_gemm), uint64_t(p->chain_pair + 1), uint64_t(p->tp_op + 1), uint64_t(p->ng0),
-                     uint64_t(p->n_elems), uint64_t(p->slot_form)})
+                     uint64_t(c.latent_mlp_width), uint64_t(c.readout_mlp_width), uint64_t(p->u_raw), uint64_t(p->pipe.channel_minor()),
+                     uint64_t(p->pipe.env_moments()), uint64_t(p->pipe.chains()), uint64_t(p->pipe.chain_pair + 1), uint64_t(p->pipe.tp_op + 1), uint64_t(p->ng0),
+                     uint64_t(p->n_elems), uint64_t(p->pipe.slot())})
     mix(v);
-  if (p->slot_form) {
+  if (p->pipe.slot()) {
     auto mixm = [&](const GemmMat& m) { mix(m.w); mix(m.wp); mix(m.wq); };
     mixm(p->s_g0f); mixm(p->s_g0ft); mixm(p->s_ro0); mixm(p->s_rstb);
     for (int l = 0; l < c.num_layers; ++l) { mixm(p->s_in[l]); mixm(p->s_rs[l]); mixm(p->s_sct[l]); }
     mix(p->o_s_wk0); mix(p->o_s_wt0);
   }
-  if (p->op_proj) {
+  if (p->pipe.op_proj) {
     auto mixs = [&](const GemmMatSet& m) { mix(m.w); mix(m.wp); mix(m.wq); mix(m.w_bs); };
     for (int l = 0; l < c.num_layers; ++l) { mixs(p->s_pr[l]); mixs(p->s_prt[l]); }
     mixs(p->s_pr0f); mixs(p->s_prt0f);
@@ -724,8 +771,8 @@ extern "C" uint64_t aa_model_plan_layout_hash(const aa_model_plan* p) {
     mix(v);
   for (int l = 0; l < c.num_layers; ++l) {
     mix(p->o_tpw[l]);
-    mix(p->env_mom ? p->o_wk[l] : 0);
-    mix(p->env_mom ? p->o_wt[l] : 0);
+    mix(p->pipe.env_moments() ? p->o_wk[l] : 0);
+    mix(p->pipe.env_moments() ? p->o_wt[l] : 0);
     mixm(p->latent[l]);
   }
   mixm(p->embed);
@@ -850,9 +897,9 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
   const int Rr = p->R;
   const bool shared = c.env_shared_weights != 0;
   const int We = shared ? u : W;  // env-weight columns of first_proj / latent outputs in the state_dict
-  auto w0_col = [&](int q) { return p->use_spec ? (q % u) * Rr + q / u : q; };  // packed col q <- reference col
+  auto w0_col = [&](int q) { return p->pipe.channel_minor() ? (q % u) * Rr + q / u : q; };  // packed col q <- reference col
   auto env_col = [&](int q) {
-    const int ch = p->use_spec ? q % u : q / Rr, r = p->use_spec ? q / u : q % Rr;
+    const int ch = p->pipe.channel_minor() ? q % u : q / Rr, r = p->pipe.channel_minor() ? q / u : q % Rr;
     return shared ? ch : ch * Rr + r;
   };
   // pack an MLP; if env_off >= 0 the LAST layer's columns [env_off, env_off+W) are env weights
@@ -906,13 +953,13 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
     gemm_pack_b(&h[p->o_g0t], NG, S, &h[p->o_g0tp]);
   }
   for (int l = 0; l < L; ++l) {
-    AA_REQUIRE(pack_mlp(p->latent[l], raw->latent[l], c.latent_mlp_depth + 1, (l < L - 1 && !p->env_mom) ? S : -1, 1,
+    AA_REQUIRE(pack_mlp(p->latent[l], raw->latent[l], c.latent_mlp_depth + 1, (l < L - 1 && !p->pipe.env_moments()) ? S : -1, 1,
                         S + (l < L - 1 ? We : 0), du, l < L - 1 ? dWe : 0, dHl),
                "pack: missing latent weights");
     AA_REQUIRE(raw->tp_weights[l], "pack: missing tp weights");
     copy(p->o_tpw[l], raw->tp_weights[l], size_t(c.tps[l].coupling ? u : 1) * c.tps[l].num_paths, 1.0);
   }
-  if (p->env_mom) {
+  if (p->pipe.env_moments()) {
     // Wenv_l[k][r][ch] (and its [r][ch][k] transpose) from the reference's [k][S + ch*R + r] columns
     auto fill = [&](int l, const double* rawm, int ka, int raw_w, double al) {
       for (int k = 0; k < ka; ++k)
@@ -942,7 +989,7 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
     AA_REQUIRE(raw->shifts, "pack: missing shifts");
     copy(p->o_shifts, raw->shifts, T, 1.0);
   }
-  if (p->o_embtab && c.embed_kind == 0) {
+  if (p->pipe.two_body_table && c.embed_kind == 0) {
     const int half = S0 / 2;
     for (int ti = 0; ti < T; ++ti)
       for (int tj = 0; tj < T; ++tj)
@@ -952,7 +999,7 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
             h[p->o_embtab + ((size_t(ti) * T + tj) * B + n) * S0 + cc] = te * h[p->o_basis + size_t(n) * S0 + cc];
           }
   }
-  if (p->o_wk0f) {
+  if (p->pipe.fold_embed_output) {
     // (fold_embed_output) env weights of layer 0 behind the output layer of scalar_embed_mlp: Wenv0'[k][r][ch] = sum_m W1[k][m] Wenv0[m][r][ch]
     const double* w1 = &h[p->embed.w[1]];  // [64, S]
     const int Rr_ = p->R, uu = c.num_tensor;
@@ -965,7 +1012,7 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
           h[p->o_wt0f + (size_t(r) * uu + ch) * 64 + k] = v;
         }
   }
-  if (p->o_embtab_h) {
+  if (p->pipe.fold_embed_table) {
     // T[pair][n][k] = sum_c tab[pair][n][c] * W0[c][k]  (W0: the packed first layer of scalar_embed_mlp, normalisation folded)
     const int H = p->embed.dims[1];
     for (int cls = 0; cls < T * T; ++cls)
@@ -977,7 +1024,7 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
         }
   }
   std::vector<const GemmMat*> slot_mats;  // (fp32 plans: bf16x3 copies are split off the rounded matrices below)
-  if (p->slot_form) {
+  if (p->pipe.slot()) {
     // slot form: every matrix below is a product / regrouping of the NORMALISED matrices packed above, formed in fp64
     const int De = c.embed_mlp_depth, Hr = c.readout_mlp_width, H = c.latent_mlp_width, NG = p->ng0, SL1 = p->SL1;
     auto put = [&](const GemmMat& m, const std::vector<double>& d) {
@@ -1067,7 +1114,7 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
   }
   struct SetRef { const GemmMatSet* m; };
   std::vector<SetRef> proj_sets;
-  if (p->op_proj) {
+  if (p->pipe.op_proj) {
     const double sf = 1.0 / std::sqrt(c.avg_num_neighbors);
     auto put_set = [&](const GemmMatSet& fw, const GemmMatSet& bw, size_t wk_off, int ka) {
       for (int r = 0; r < Rr; ++r) {
@@ -1084,7 +1131,7 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
       proj_sets.push_back({&bw});
     };
     for (int l = 0; l < L; ++l) put_set(p->s_pr[l], p->s_prt[l], p->o_wk[l], l == 0 ? S : c.latent_mlp_width);
-    if (p->slot_form) put_set(p->s_pr0f, p->s_prt0f, p->o_s_wk0, S);
+    if (p->pipe.slot()) put_set(p->s_pr0f, p->s_prt0f, p->o_s_wk0, S);
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (c.dtype == AA_F64) {
@@ -1109,7 +1156,7 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
     for (const GemmMat* m : slot_mats) splitw(m->w, m->K, m->N, m->wq);
     for (const SetRef& sr : proj_sets)
       for (int r = 0; r < sr.m->count; ++r) splitw(sr.m->w + r * sr.m->w_bs, sr.m->K, sr.m->N, sr.m->wq + r * sr.m->wq_bs);
-    if (p->chain_gemm) {
+    if (p->pipe.chains()) {
       const int SL = S * L, SL1 = p->SL1, N2 = SL + c.num_tensor;
       const float* rt = &hf[p->readout.wt[0]];          // [64, SL1]  (transposed first readout layer)
       const float* lt = &hf[p->latent[L - 1].wt[0]];    // [64, N2]   (transposed first layer of the last latent)
@@ -1128,7 +1175,7 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
       gemm_pack_bf16x3(b.data(), 128, SL, reinterpret_cast<unsigned*>(&hf[p->o_b3b_q]));
       gemm_pack_bf16x3(cmat.data(), 64, c.num_tensor, reinterpret_cast<unsigned*>(&hf[p->o_b3c_q]));
     }
-    if (p->o_g0fq) {
+    if (p->pipe.fold_embed_output) {
       // (fold_embed_output) first stage behind the output layer of scalar_embed_mlp: W1 @ G0 and its transpose
       const int NG = p->ng0;
       std::vector<float> gf(size_t(64) * NG), gft(size_t(NG) * 64);
@@ -1142,7 +1189,7 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
       gemm_pack_bf16x3(gf.data(), 64, NG, reinterpret_cast<unsigned*>(&hf[p->o_g0fq]));
       gemm_pack_bf16x3(gft.data(), NG, 64, reinterpret_cast<unsigned*>(&hf[p->o_g0tfq]));
     }
-    if (p->o_lat1in_fq) {
+    if (p->pipe.fold_latent_outputs) {
       // folded first layers (fold_latent_outputs): row block "lat_l" of a consumer's first layer <- Wout_l @ that block, in fp64 from the
       // normalised matrices, rounded once.  Row order of the consumers: [two-body | lat0 | scal1] (latent 1), [two-body | lat0 | lat1] (readout)
       const double* wo0 = &h[p->latent[0].w[1]];  // [64, 64] output layer of latent 0
@@ -1184,7 +1231,7 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
         const float* rt = &hf[p->readout.wt[0]];
         const float* lt = &hf[p->latent[L - 1].wt[0]];
         const int N2 = SL + c.num_tensor, SL1_ = p->SL1;
-        if (p->o_b3bf_q) {
+        if (p->pipe.fold_lat0_reverse) {
         std::vector<double> b(size_t(128) * SL);
         for (int k = 0; k < 64; ++k)
           for (int n = 0; n < SL; ++n) {
@@ -1229,12 +1276,12 @@ struct Workspace {
 // per 64-channel slice for the x1 path plus one per 64-wide block of every layer's env input
 static int num_gsh_slots(const aa_model_plan* p) {
   const aa_model_config& c = p->cfg;
-  if (p->tp_op >= 0) {
+  if (p->pipe.tp_op >= 0) {
     int n = c.num_tensor / 64;
     for (int l = 0; l < c.num_layers; ++l) n += (l == 0 ? c.num_scalar : c.latent_mlp_width) / 64;
     return n;
   }
-  return p->use_spec ? c.num_layers + 1 : 1;
+  return p->pipe.channel_minor() ? c.num_layers + 1 : 1;
 }
 
 static Workspace layout_workspace(const aa_model_plan* p, int64_t N, int64_t E, int with_forces) {
@@ -1258,9 +1305,9 @@ static Workspace layout_workspace(const aa_model_plan* p, int64_t N, int64_t E, 
   w.fcat = take(Ez * p->SL1);
   size_t dmax = 1;
   for (int l = 0; l < L; ++l) {
-    if (!p->env_mom) w.envw[l] = take(Ez * p->W);
+    if (!p->pipe.env_moments()) w.envw[l] = take(Ez * p->W);
     w.x2s[l] = take(Nz * u * p->D);
-    if (l < L - 1 && p->chain_pair < 0 && !p->env_mom) {
+    if (l < L - 1 && p->pipe.chain_pair < 0 && !p->pipe.env_moments()) {
       w.tf[l] = take(Ez * u * c.tps[l].dout);
       dmax = std::max(dmax, size_t(c.tps[l].dout));
     }
@@ -1268,14 +1315,14 @@ static Workspace layout_workspace(const aa_model_plan* p, int64_t N, int64_t E, 
     for (int i = 0; i < c.latent_mlp_depth; ++i) w.lat_h[l][i] = take(Ez * c.latent_mlp_width);
   }
   for (int i = 0; i < c.readout_mlp_depth; ++i) w.ro_h[i] = take(Ez * c.readout_mlp_width);
-  if (p->chain_gemm) w.e_edge = take(Ez);
-  if (p->embed_fused) w.trev = take(Ez * 8);
-  if (p->fused_fwd) w.tiles = take(((3 * Nz + 8) * sizeof(int32_t) + es - 1) / es);  // class lists + counters of the team form
+  if (p->pipe.chains()) w.e_edge = take(Ez);
+  if (p->pipe.embed_fused) w.trev = take(Ez * 8);
+  if (p->pipe.fused_fwd) w.tiles = take(((3 * Nz + 8) * sizeof(int32_t) + es - 1) / es);  // class lists + counters of the team form
   if (with_forces) {
     w.dvec = take(Ez * 4);
     w.vir_part = take((size_t(kVirialBlocks) * 9 * sizeof(double) + es - 1) / es);
   }
-  if (p->tp_op >= 0) {
+  if (p->pipe.tp_op >= 0) {
     w.bvec_op = take(Nz * L * p->D * u);
     w.mom_op = take(Nz * p->D * size_t(std::max(c.num_scalar, c.latent_mlp_width)));
   }
@@ -1284,10 +1331,10 @@ static Workspace layout_workspace(const aa_model_plan* p, int64_t N, int64_t E, 
     for (int i = 0; i < c.readout_mlp_depth; ++i) w.g_ro_h[i] = take(Ez * c.readout_mlp_width);
     for (int i = 0; i < c.latent_mlp_depth; ++i) w.g_lat_h[i] = take(Ez * c.latent_mlp_width);
     for (int l = 0; l < L; ++l) w.g_scal[l] = take(Ez * u);
-    if (!p->env_mom) w.g_envw = take(Ez * p->W);
-    if (p->env_mom) w.g_aenv = take(Ez * size_t(std::max(S, c.latent_mlp_width)));
+    if (!p->pipe.env_moments()) w.g_envw = take(Ez * p->W);
+    if (p->pipe.env_moments()) w.g_aenv = take(Ez * size_t(std::max(S, c.latent_mlp_width)));
     w.g_w0 = take(Ez * p->W);
-    if (L > 1 && p->chain_pair < 0) {
+    if (L > 1 && p->pipe.chain_pair < 0) {
       w.g_tf[0] = take(Ez * u * dmax);
       w.g_tf[1] = L > 2 ? take(Ez * u * dmax) : w.g_tf[0];
     }
@@ -1295,10 +1342,10 @@ static Workspace layout_workspace(const aa_model_plan* p, int64_t N, int64_t E, 
     for (int i = 0; i < c.embed_mlp_depth; ++i) w.g_se_h[i] = take(Ez * c.embed_mlp_width);
     w.g_emb0 = take(Ez * S0);
     w.g_sh = take(Ez * p->D * num_gsh_slots(p));  // slot 0: x1 path of layer 0; slot l+1: env path of layer l (see num_gsh_slots)
-    if (p->tp_op >= 0) {
+    if (p->pipe.tp_op >= 0) {
       w.q_op = take(Nz * L * p->D * u);
       w.gm_op = take(Nz * p->D * size_t(std::max(c.num_scalar, c.latent_mlp_width)));
-      if (p->op_proj) w.dx2s_op = take(Nz * p->D * u);
+      if (p->pipe.op_proj) w.dx2s_op = take(Nz * p->D * u);
     }
   }
   w.total = o;
@@ -1377,6 +1424,14 @@ struct Runner {
   T* buf(size_t off) const { return reinterpret_cast<T*>(ws + off); }
   const T* wt(size_t off) const { return wts + off; }
 
+  // the plan's kernel-selection options of the linear layers
+  void gemm_options(GemmArgs& g) const {
+    g.force_kernel = p->opt.gemm_valu ? 3 : (p->opt.gemm_fp32_mfma ? 1 : 0);
+    g.opt_v1 = p->opt.gemm_v1;
+    g.opt_lds_epilogue = p->opt.gemm_lds_epilogue;
+    g.opt_f64_column_loop = p->opt.f64_column_loop;
+    g.opt_f64_rows = p->opt.f64_rows;
+  }
   int gemm(const SegList& a, int act_a, const GemmMat& m, const SegList& c, const SegList* z = nullptr, const SegList* add = nullptr, int act_lo = 0,
            int act_hi = 0) {
     return gemm(a, act_a, wt(m.w), wt(m.wp), wt(m.wq), m.K, m.N, c, nullptr, z, add, act_lo, act_hi);
@@ -1399,11 +1454,7 @@ struct Runner {
     if (z) g.z = *z;
     g.act_a = act_a;
     g.act_kind = act_now;
-    g.force_kernel = p->opt.gemm_valu ? 3 : (p->opt.gemm_fp32_mfma ? 1 : 0);
-    g.opt_v1 = p->opt.gemm_v1;
-    g.opt_lds_epilogue = p->opt.gemm_lds_epilogue;
-    g.opt_f64_column_loop = p->opt.f64_column_loop;
-    g.opt_f64_rows = p->opt.f64_rows;
+    gemm_options(g);
     g.has_add = add ? 1 : 0;
     if (add) g.add = *add;
     if (int rc = launch_gemm<T>(g, stream)) return rc;
@@ -1482,7 +1533,7 @@ struct Runner {
     a.basis_w = wt(p->o_basis);
     a.embed_kind = c.embed_kind;
     a.spline_span = c.spline_span;
-    a.emb_tab = p->o_embtab ? wt(p->o_embtab) : nullptr;
+    a.emb_tab = p->pipe.two_body_table ? wt(p->o_embtab) : nullptr;
     a.vec = buf(w.vec);
     a.sh = buf(w.sh);
     a.emb0 = buf(w.emb0);
@@ -1514,7 +1565,7 @@ struct Runner {
     r.scales = c.has_scales ? wt(p->o_scales) : nullptr;
     r.shifts = c.has_shifts ? wt(p->o_shifts) : nullptr;
     r.atom_energy = atom_energy;
-    r.edge_sum = (p->chain_gemm && atom_energy) ? buf(w.e_edge) : nullptr;  // written by the forward readout chain
+    r.edge_sum = (p->pipe.chains() && atom_energy) ? buf(w.e_edge) : nullptr;  // written by the forward readout chain
     return r;
   }
 
@@ -1552,7 +1603,7 @@ struct Runner {
     return a;
   }
 
-  // ---- fused GEMM chains (plan->chain_gemm) -------------------------------------------------------------
+  // ---- fused GEMM chains (LinearPath::Chains) -------------------------------------------------------------
   static ChainLayer chain_layer(int64_t M, const SegList& a, int act_a, const void* Bq, int K, int Nn, const SegList& c,
                                 const int* accum, const SegList* z, const SegList* add, int use_prev, int keep_tile,
                                 int keep_act) {
@@ -1612,8 +1663,8 @@ struct Runner {
     return m;
   }
 
-  // slot form of the single-layer pipeline (aa_model_plan::slot_form); the debug taps name tensors it never forms
-  bool use_slot() const { return p->slot_form && !p->taps; }
+  // slot form of the single-layer pipeline (LinearPath::Slot); the debug taps name tensors it never forms
+  bool use_slot() const { return p->pipe.slot() && !p->taps; }
 
   TpOpArgs op_args(const aa_graph* g, int l) const {
     const aa_model_config& c = p->cfg;
@@ -1676,10 +1727,10 @@ struct Runner {
     return o;
   }
 
-  // env projections of the operator kernels as batched linear-layer launches (aa_model_plan::op_proj): where there are enough
+  // env projections of the operator kernels as batched linear-layer launches (ModelPipeline::op_proj): where there are enough
   // atoms to fill the chip with 128-row tiles
   bool use_proj(const aa_graph* g) const {
-    if (!(p->op_proj && w.bvec_op && w.mom_op && !p->opt.tp_operator_fused)) return false;
+    if (!(p->pipe.op_proj && w.bvec_op && w.mom_op && !p->opt.tp_operator_fused)) return false;
     if (p->opt.op_proj_gemm == 1) return true;
     return atom_end(g) - atom_begin(g) >= 4096;
   }
@@ -1695,11 +1746,7 @@ struct Runner {
     gm.Bp = wt(ms.wp);
     gm.Bq = sizeof(T) == 4 ? wt(ms.wq) : nullptr;
     gm.act_kind = AA_ACT_SILU;
-    gm.force_kernel = p->opt.gemm_valu ? 3 : (p->opt.gemm_fp32_mfma ? 1 : 0);
-    gm.opt_v1 = p->opt.gemm_v1;
-    gm.opt_lds_epilogue = p->opt.gemm_lds_epilogue;
-    gm.opt_f64_column_loop = p->opt.f64_column_loop;
-    gm.opt_f64_rows = p->opt.f64_rows;
+    gemm_options(gm);
     gm.batch = p->D;
     gm.a_bs = a_bs;
     gm.c_bs = c_bs;
@@ -1720,14 +1767,14 @@ struct Runner {
     o.scal = buf(w.scal[l]);
     if (use_proj(g)) {
       o.proj_gemm = 1;
-      if (int rc = launch_tp_op<T>(p->tp_op, l, false, o, stream, 1)) return rc;
+      if (int rc = launch_tp_op<T>(p->pipe.tp_op, l, false, o, stream, 1)) return rc;
       if (int rc = mark("tp_op_moments", p->D + o.ka)) return rc;
       const GemmMatSet& ms = (l == 0 && use_slot()) ? p->s_pr0f : p->s_pr[l];
       if (int rc = proj_gemm(o, ms, buf(w.mom_op), int64_t(p->D) * o.ka, o.ka, buf(w.x2s[l]), int64_t(p->D) * u, u)) return rc;
-      if (int rc = launch_tp_op<T>(p->tp_op, l, false, o, stream, 2)) return rc;
+      if (int rc = launch_tp_op<T>(p->pipe.tp_op, l, false, o, stream, 2)) return rc;
       return mark("tp_op_fwd", p->W + u, double(l + 1) * p->D * u);
     }
-    if (int rc = launch_tp_op<T>(p->tp_op, l, false, o, stream)) return rc;
+    if (int rc = launch_tp_op<T>(p->pipe.tp_op, l, false, o, stream)) return rc;
     return mark("tp_op_fwd", p->D + o.ka + p->W + u, double(l + 1) * p->D * u);
   }
   // reverse of tensor-product layer l on the operator kernels: d scal_m -> d w0 / d Y (layer 0), d (env input) -> g_aenv
@@ -1749,14 +1796,14 @@ struct Runner {
     if (use_proj(g) && w.dx2s_op) {
       o.proj_gemm = 1;
       o.dx2s = buf(w.dx2s_op);
-      if (int rc = launch_tp_op<T>(p->tp_op, l, true, o, stream, 1)) return rc;
+      if (int rc = launch_tp_op<T>(p->pipe.tp_op, l, true, o, stream, 1)) return rc;
       if (int rc = mark("tp_op_bwd", elems - 2 * o.ka - p->D, double(L) * p->D * u)) return rc;
       const GemmMatSet& ms = (l == 0 && use_slot()) ? p->s_prt0f : p->s_prt[l];
       if (int rc = proj_gemm(o, ms, buf(w.dx2s_op), int64_t(p->D) * u, u, buf(w.gm_op), int64_t(p->D) * o.ka, o.ka)) return rc;
-      if (int rc = launch_tp_op<T>(p->tp_op, l, true, o, stream, 2)) return rc;
+      if (int rc = launch_tp_op<T>(p->pipe.tp_op, l, true, o, stream, 2)) return rc;
       return mark("tp_op_edge_env", 2 * o.ka + p->D);
     }
-    if (int rc = launch_tp_op<T>(p->tp_op, l, true, o, stream)) return rc;
+    if (int rc = launch_tp_op<T>(p->pipe.tp_op, l, true, o, stream)) return rc;
     return mark("tp_op_bwd", elems, double(L) * p->D * u);
   }
 
@@ -1771,7 +1818,7 @@ struct Runner {
 
   // the whole forward in one launch (aa_fused.hip): every center atom's edge segment fits one 32-row MFMA tile
   bool use_fused_fwd(const aa_graph* g) const {
-    if (!(sizeof(T) == 4 && p->fused_fwd && !p->taps && g->max_degree > 0 && g->max_degree <= kFusedMaxDegree)) return false;
+    if (!(sizeof(T) == 4 && p->pipe.fused_fwd && !p->taps && g->max_degree > 0 && g->max_degree <= kFusedMaxDegree)) return false;
     // (three species + the team exchange area exceed the 160 KB of LDS: such graphs run the staged pipeline)
     if (fused_fwd_lds_bytes(p->cfg.num_types, g->max_degree > 32) > size_t(160) * 1024) return false;
     if (g->max_degree <= 32) return true;  // one full-ish tile per atom: faster than the staged forward at every size
@@ -1797,7 +1844,7 @@ struct Runner {
   // a_0 are stored where the embedding / lat_0 used to be (ChainLayer::kept_out), consumers run on the folded matrices.  What
   // graphs with long segments -- dense systems, too large for the team form -- run.
   bool fold_staged() const {
-    return p->chain_gemm && p->tp_op < 0 && p->o_g0fq && p->o_lat1in_fq && p->o_wk0f && p->cfg.num_layers == 2 && !p->taps &&
+    return p->pipe.chains() && p->pipe.tp_op < 0 && p->pipe.fold_embed_output && p->pipe.fold_latent_outputs && p->cfg.num_layers == 2 && !p->taps &&
            !p->opt.staged_no_fold;
   }
   // did the forward of this step leave a_e in the embedding's slot (folded first stage / env weights in the reverse)?
@@ -1814,11 +1861,11 @@ struct Runner {
   int fused_form(const FusedFwdArgs& a, FusedForm* form) const {
     *form = FusedForm::OneWave;
     const bool teams = a.tile_atoms != nullptr;
-    if (!p->fused_wide || !a.w0 || (teams && !a.mixed)) return AA_OK;
+    if (!p->pipe.fused_wide || !a.w0 || (teams && !a.mixed)) return AA_OK;
     const int cus = device_cu_count();
     if (cus < 0) return cus;
     const int64_t n = a.atom_end - a.atom0;
-    const bool tail_ok = want_forces && !teams && p->chain_gemm && p->o_b3af_q && p->o_b3c_q && p->cfg.num_layers == 2;
+    const bool tail_ok = want_forces && !teams && p->pipe.chains() && p->pipe.fold_latent_outputs && p->cfg.num_layers == 2;
     if (p->opt.fused_narrow == 2) {
       *form = tail_ok ? FusedForm::EightWaveTail : FusedForm::EightWave;
     } else if (p->opt.fused_narrow == 3) {
@@ -1866,7 +1913,7 @@ struct Runner {
     a.bessel_w = wf(p->o_bessel);
     a.emb_tab = wf(p->o_embtab_h);  // (folded: the table yields the first layer's pre-activation)
     // the weight program of the kernel (see fused_fwd_kernel): 12-KB blocks in execution order.  The plan takes the fused forward
-    // only with every fold of its program packed (aa_model_plan_create: o_embtab_h, o_g0fq, o_lat1in_fq)
+    // only with every fold of its program packed (choose_pipeline: fold_embed_table, fold_embed_output, fold_latent_outputs)
     int ns = 0;
     FusedFwdArgs* prog = &a;  // (the program under construction: `a`, later the two-waves-per-SIMD form's copy)
     auto add_layer = [&](const float* Wq, int KC, int tile0, int ntiles) {
@@ -1941,7 +1988,7 @@ struct Runner {
       const bool tail = form == FusedForm::EightWaveTail;
       if (tail) {
         add_layer(wf(p->o_b3af_q), 2, 0, 2);
-        add_layer(wf(p->o_b3bf_q ? p->o_b3bf_q : p->o_b3b_q), 4, 0, 4);
+        add_layer(wf(p->pipe.fold_lat0_reverse ? p->o_b3bf_q : p->o_b3b_q), 4, 0, 4);
         add_layer(wf(p->o_b3c_q), 2, 0, 2);
         a8.g_fcat = bf(w.g_fcat);
         a8.ld_gfcat = p->SL1;
@@ -1950,7 +1997,7 @@ struct Runner {
       if (ns != fused_fwd8_num_steps(p->R, tail)) return fail(AA_ERR_INVALID, "fused forward (wide): program length mismatch");
     }
     if (int rc = mark("begin")) return rc;
-    if (int rc = launch_fused_fwd(p->chain_pair, form, a, form != FusedForm::OneWave ? &a8 : nullptr, stream)) return rc;
+    if (int rc = launch_fused_fwd(p->pipe.chain_pair, form, a, form != FusedForm::OneWave ? &a8 : nullptr, stream)) return rc;
     fwd_b3_done = form == FusedForm::EightWaveTail && a.atom_end > a.atom0;  // (an empty block launches nothing)
     // algorithmic traffic: neighbor id + shift in; unit vector, harmonics, five 64-wide rows and w0 out per edge;
     // position, two x2s blocks, energy, row pointer per atom.  Flops: the linear layers of the forward (w0 counted once).
@@ -1976,7 +2023,7 @@ struct Runner {
     const SegList none{0, {}};
     const bool slot = use_slot();
     const bool fstaged = fold_staged();
-    if (p->chain_gemm) {
+    if (p->pipe.chains()) {
       // 3 + 4 + 5a as ONE kernel: emb0 -> h_e -> emb -> [two_body | w0]; hidden layers stay in registers
       ChainArgs ca{};
       ca.nlayers = 3;
@@ -2015,7 +2062,7 @@ struct Runner {
     {
       SegList in{1, {seg(buf(w.emb), S, S)}};
       SegList out{3, {seg(buf(w.fcat), SL1, S), seg(buf(w.w0), W, W), seg(buf(w.envw[0]), W, W)}};
-      if (p->env_mom) out.count = 2;
+      if (p->pipe.env_moments()) out.count = 2;
       act_now = AA_ACT_SILU;  // (a plain linear map: no activation involved)
       if (int rc = gemm(in, 0, wt(p->o_g0), wt(p->o_g0p), wt(p->o_g0q), S, p->ng0, out, nullptr, nullptr)) return rc;
     }
@@ -2023,23 +2070,23 @@ struct Runner {
     // 5: layers
     const double sfac = 1.0 / std::sqrt(c.avg_num_neighbors);
     for (int l = 0; l < L; ++l) {
-      if (p->tp_op >= 0) {
+      if (p->pipe.tp_op >= 0) {
         if (int rc = run_op_fwd(g, l)) return rc;
-      } else if (p->env_mom) {
+      } else if (p->pipe.env_moments()) {
         TpMomArgs m = mom_args(g);
         if (l == 0) {
           m.c.scal1 = buf(w.scal[0]);  // the first-layer kernel writes its scalars through this field
           if (fstaged) m.wk0 = wt(p->o_wk0f);  // (its env input is a_e: env weights behind the output layer of scalar_embed_mlp)
-          if (int rc = launch_tp_mom_fwd_first<T>(p->chain_pair, m, stream)) return rc;
+          if (int rc = launch_tp_mom_fwd_first<T>(p->pipe.chain_pair, m, stream)) return rc;
           if (int rc = mark("tp_mom_fwd_first", p->D + m.ka0 + W + u, double(p->D) * u)) return rc;
         } else {
-          if (int rc = launch_tp_mom_fwd_last<T>(p->chain_pair, m, stream)) return rc;
+          if (int rc = launch_tp_mom_fwd_last<T>(p->pipe.chain_pair, m, stream)) return rc;
           if (int rc = mark("tp_mom_fwd_last", p->D + m.ka1 + W + u, 2.0 * p->D * u)) return rc;
         }
-      } else if (p->chain_pair >= 0 && l == 1) {
-        if (int rc = launch_tp_chain_fwd_last<T>(p->chain_pair, chain_args(g), stream)) return rc;
+      } else if (p->pipe.chain_pair >= 0 && l == 1) {
+        if (int rc = launch_tp_chain_fwd_last<T>(p->pipe.chain_pair, chain_args(g), stream)) return rc;
         if (int rc = mark("tp_chain_fwd_last", 2 * W + p->D + u, 2.0 * p->D * u)) return rc;
-      } else if (p->use_spec) {
+      } else if (p->pipe.channel_minor()) {
         TpSpecFwdArgs a{};
         a.E = E;
         a.N = N;
@@ -2059,10 +2106,10 @@ struct Runner {
         a.coupling = c.tps[l].coupling;
         a.sf = sfac;
         a.x2s = buf(w.x2s[l]);
-        a.out = (l < L - 1 && p->chain_pair < 0) ? buf(w.tf[l]) : nullptr;
+        a.out = (l < L - 1 && p->pipe.chain_pair < 0) ? buf(w.tf[l]) : nullptr;
         a.scal = buf(w.scal[l]);
         a.ld_scal = u;
-        if (int rc = launch_tp_spec_fwd<T>(p->spec_sig[l], a, stream)) return rc;
+        if (int rc = launch_tp_spec_fwd<T>(p->pipe.spec_sig[l], a, stream)) return rc;
         if (int rc = mark("tp_spec_fwd", 2 * W + p->D + u, 2.0 * p->D * u)) return rc;
       } else {
       TpLayerFwdArgs a{};
@@ -2083,7 +2130,7 @@ struct Runner {
       if (int rc = launch_tp_layer_fwd<T>(p->layers[l], a, stream)) return rc;
       if (int rc = mark("tp_layer_fwd", 2 * W + p->D + u * p->D + u, 2.0 * p->D * u)) return rc;
       }
-      if (p->chain_gemm) {
+      if (p->pipe.chains()) {
         ChainArgs ca{};
         SegList in{2, {seg(buf(w.fcat), SL1, S * (l + 1)), seg(buf(w.scal[l]), u, u)}};
         SegList ch{1, {seg(buf(w.lat_h[l][0]), 64, 64)}};
@@ -2130,13 +2177,13 @@ struct Runner {
       }
       SegList in{2, {seg(buf(w.fcat), SL1, S * (l + 1)), seg(buf(w.scal[l]), u, u)}};
       SegList out;
-      out.count = (l < L - 1 && !p->env_mom) ? 2 : 1;
+      out.count = (l < L - 1 && !p->pipe.env_moments()) ? 2 : 1;
       out.s[0] = seg(buf(w.fcat) + S * (l + 1), SL1, S);
-      if (l < L - 1 && !p->env_mom) out.s[1] = seg(buf(w.envw[l + 1]), W, W);
+      if (l < L - 1 && !p->pipe.env_moments()) out.s[1] = seg(buf(w.envw[l + 1]), W, W);
       if (int rc = mlp_fwd(p->latent[l], c.latent_mlp_depth + 1, in, w.lat_h[l], out, 1)) return rc;
     }
     // 6: edge readout GEMM layers, 7-8: last linear + edge sum + per-type scale/shift
-    if (c.readout_mlp_depth > 0 && !p->chain_gemm) {
+    if (c.readout_mlp_depth > 0 && !p->pipe.chains()) {
       act_now = c.act_kind[2];
       SegList a{1, {seg(buf(w.fcat), SL1, SL1)}};
       for (int i = 0; i < c.readout_mlp_depth; ++i) {
@@ -2153,10 +2200,10 @@ struct Runner {
       }
     }
     ReadoutArgs ra = readout_args(g, atom_energy);
-    ro_grad_done = want_forces && !p->chain_gemm && c.readout_mlp_depth > 0 && !p->opt.readout_two_pass;
+    ro_grad_done = want_forces && !p->pipe.chains() && c.readout_mlp_depth > 0 && !p->opt.readout_two_pass;
     if (ro_grad_done) ra.g_h = buf(w.g_ro_h[c.readout_mlp_depth - 1]);
     if (int rc = launch_readout_reduce<T>(ra, stream)) return rc;
-    return mark("readout_reduce", (p->chain_gemm ? 1 : (c.readout_mlp_depth > 0 ? c.readout_mlp_width : SL1)) * (ro_grad_done ? 2.0 : 1.0), 1);
+    return mark("readout_reduce", (p->pipe.chains() ? 1 : (c.readout_mlp_depth > 0 ? c.readout_mlp_width : SL1)) * (ro_grad_done ? 2.0 : 1.0), 1);
   }
 
   // geometry reverse + force assembly (the end of every reverse pass)
@@ -2169,12 +2216,12 @@ struct Runner {
     eb.g_sh = buf(w.g_sh);
     eb.num_gsh = num_gsh;
     eb.forces = forces;
-    if (p->embed_fused) eb.t_in = buf(w.trev);
+    if (p->pipe.embed_fused) eb.t_in = buf(w.trev);
     const bool gather = g->t_rowptr && g->t_perm;
     eb.dvec = buf(w.dvec);
     eb.gather = gather ? 1 : 0;
     if (int rc = launch_edge_backward<T>(eb, stream)) return rc;
-    if (int rc = mark("edge_backward", 8.0 / sizeof(T) + 4 + (p->embed_fused ? c.num_bessels : c.embed_dim) + double(num_gsh) * p->D + (gather ? 4 : 6))) return rc;
+    if (int rc = mark("edge_backward", 8.0 / sizeof(T) + 4 + (p->pipe.embed_fused ? c.num_bessels : c.embed_dim) + double(num_gsh) * p->D + (gather ? 4 : 6))) return rc;
     if (gather) {
       // deterministic force assembly: per atom, own segment minus transposed segment, fixed order (no atomics)
       ForceGatherArgs fg{N, g->rowptr, g->t_rowptr, g->t_perm, buf(w.dvec), forces};
@@ -2184,7 +2231,7 @@ struct Runner {
     return AA_OK;
   }
 
-  // Reverse pass of the slot form (aa_model_plan::slot_form): per dense-net slot, top down.  Every layer here has a 128-wide (S)
+  // Reverse pass of the slot form (LinearPath::Slot): per dense-net slot, top down.  Every layer here has a 128-wide (S)
   // output -- the accumulator-resident kernel's shape -- and writes its slot once.
   int backward_slot(const aa_graph* g, const void* pos, void* forces) {
     const aa_model_config& c = p->cfg;
@@ -2247,15 +2294,15 @@ struct Runner {
     const aa_model_config& c = p->cfg;
     const int S = c.num_scalar, u = c.num_tensor, L = c.num_layers, W = p->W, SL1 = p->SL1;
     // spec path with u <= 64 writes every g_sh slot with plain stores; otherwise slots are accumulated into
-    const bool gsh_stores = (p->use_spec && u <= 64) || p->tp_op >= 0;
+    const bool gsh_stores = (p->pipe.channel_minor() && u <= 64) || p->pipe.tp_op >= 0;
     const int num_gsh = num_gsh_slots(p);
     if (!gsh_stores) AA_CHECK_HIP(hipMemsetAsync(buf(w.g_sh), 0, size_t(E) * p->D * num_gsh * sizeof(T), stream));
     if (!(g->t_rowptr && g->t_perm)) AA_CHECK_HIP(hipMemsetAsync(forces, 0, size_t(N) * 3 * sizeof(T), stream));
     if (int rc = mark("memset", gsh_stores ? 0 : p->D * num_gsh, 3)) return rc;
     const SegList none{0, {}};
-    if (p->chain_gemm && fwd_b3_done) {
+    if (p->pipe.chains() && fwd_b3_done) {
       // (the fused forward of this step ran this chain in its tail: d EDGE_FEATURES[:, :S L] and d scal_{L-1} are in the workspace)
-    } else if (p->chain_gemm) {
+    } else if (p->pipe.chains()) {
       // readout reverse + last latent reverse in ONE kernel; d_lat_{L-1} and d_h never leave registers
       ReadoutArgs r = readout_args(g, nullptr);
       ChainArgs ca{};
@@ -2281,12 +2328,12 @@ struct Runner {
       ca.L[2] = chain_layer(E, in, 0, wt(p->o_b3b_q), 128, S * L, c2, nullptr, nullptr, nullptr, 1, -1, 0);
       ca.L[2].a_mode = 1;
       ca.L[3] = chain_layer(E, none, 0, wt(p->o_b3c_q), 64, u, c3, nullptr, nullptr, nullptr, 1, -1, 0);
-      if (p->o_b3af_q && L == 2) {
+      if (p->pipe.fold_latent_outputs && L == 2) {
         // "d lat1 = d ro_h @ Wro[lat1]^T" and "d a1 = d lat1 @ Wout_1^T" as ONE 64x64 layer (folded at pack time): 12 instead of 14 steps
         ca.nlayers = 3;
         ca.L[0] = chain_layer(E, in, 0, wt(p->o_b3af_q), 64, 64, cn, nullptr, &z1, nullptr, 0, 0, 0);
         ca.L[0].a_mode = 1;
-        ca.L[1] = chain_layer(E, in, 0, wt(p->o_b3bf_q ? p->o_b3bf_q : p->o_b3b_q), 128, S * L, c2, nullptr, nullptr, nullptr, 1, -1, 0);
+        ca.L[1] = chain_layer(E, in, 0, wt(p->pipe.fold_lat0_reverse ? p->o_b3bf_q : p->o_b3b_q), 128, S * L, c2, nullptr, nullptr, nullptr, 1, -1, 0);
         ca.L[1].a_mode = 1;
         ca.L[2] = chain_layer(E, none, 0, wt(p->o_b3c_q), 64, u, c3, nullptr, nullptr, nullptr, 1, -1, 0);
       }
@@ -2327,9 +2374,9 @@ struct Runner {
     const double sfac = 1.0 / std::sqrt(c.avg_num_neighbors);
     for (int l = L - 1; l >= 0; --l) {
       // latent MLP reverse
-      if (p->chain_gemm && l == L - 1) {
+      if (p->pipe.chains() && l == L - 1) {
         // (already done inside the readout chain above)
-      } else if (p->chain_gemm) {
+      } else if (p->pipe.chains()) {
         ChainArgs ca{};
         ca.nlayers = 2;
         SegList in{1, {seg(buf(w.g_fcat) + S * (l + 1), SL1, S)}};
@@ -2340,7 +2387,7 @@ struct Runner {
         int acc1[3] = {1, 0, 0};
         ca.L[0] = chain_layer(E, in, 0, wt(p->latent[l].wtq[1]), S, 64, cn, nullptr, &zz, &ad, 0, 0, 0);
         ca.L[1] = chain_layer(E, none, 0, wt(p->latent[l].wtq[0]), 64, S * (l + 1) + u, c1, acc1, nullptr, nullptr, 1, -1, 0);
-        if (p->o_b3bf_q && L == 2 && l == 0) {
+        if (p->pipe.fold_lat0_reverse && L == 2 && l == 0) {
           // the readout-reverse chain already applied Wout_0^T (folded into its lat0 columns): what is left of the output layer's
           // reverse is elementwise -- d h = (d a_0 + d a_0 of the moments) x silu'(h) -- and rides as the operand transform of the
           // first-layer reverse: ONE layer, 4 steps instead of 6
@@ -2376,21 +2423,21 @@ struct Runner {
       b2_done:;
       } else {
       SegList go;
-      go.count = (l < L - 1 && !p->env_mom) ? 2 : 1;
+      go.count = (l < L - 1 && !p->pipe.env_moments()) ? 2 : 1;
       go.s[0] = seg(buf(w.g_fcat) + S * (l + 1), SL1, S);
-      if (l < L - 1 && !p->env_mom) go.s[1] = seg(buf(w.g_envw), W, W);
-      SegList aenv{1, {seg(p->env_mom ? buf(w.g_aenv) : nullptr, c.latent_mlp_width, c.latent_mlp_width)}};
-      const SegList* addp = (p->env_mom && l < L - 1) ? &aenv : nullptr;
+      if (l < L - 1 && !p->pipe.env_moments()) go.s[1] = seg(buf(w.g_envw), W, W);
+      SegList aenv{1, {seg(p->pipe.env_moments() ? buf(w.g_aenv) : nullptr, c.latent_mlp_width, c.latent_mlp_width)}};
+      const SegList* addp = (p->pipe.env_moments() && l < L - 1) ? &aenv : nullptr;
       SegList gi{2, {seg(buf(w.g_fcat), SL1, S * (l + 1)), seg(buf(w.g_scal[l]), u, u)}};
       int acc[3] = {1, 0, 0};
       if (int rc = mlp_bwd(p->latent[l], c.latent_mlp_depth + 1, go, w.lat_h[l], w.g_lat_h, gi, acc, 1, addp)) return rc;
       }
       // tensor-product layer reverse
-      if (p->tp_op >= 0) {
+      if (p->pipe.tp_op >= 0) {
         if (int rc = run_op_bwd(g, l)) return rc;
         continue;
       }
-      if (p->env_mom) {
+      if (p->pipe.env_moments()) {
         TpMomArgs m = mom_args(g);
         m.c.gscal0 = buf(w.g_scal[0]);
         m.c.gscal1 = buf(w.g_scal[1]);
@@ -2400,19 +2447,19 @@ struct Runner {
         m.g_a = buf(w.g_aenv);
         if (l == 1) {
           m.ld_ga = c.latent_mlp_width;
-          if (int rc = launch_tp_mom_bwd_last<T>(p->chain_pair, m, stream)) return rc;
+          if (int rc = launch_tp_mom_bwd_last<T>(p->pipe.chain_pair, m, stream)) return rc;
           if (int rc = mark("tp_mom_bwd_last", p->D + W + u + 2 * m.ka1 + p->D, double(p->D) * u)) return rc;
         } else {
           m.ld_ga = S;
           // (after a fused forward the embedding's slot holds a_e = silu(h) of scalar_embed_mlp and the env weights are folded behind
           //  its output layer, fold_embed_output: d a_e comes out instead of d emb)
-          if (p->o_wt0f && folded_fwd(g)) m.wt0 = wt(p->o_wt0f);
-          if (int rc = launch_tp_mom_bwd_first<T>(p->chain_pair, m, stream)) return rc;
+          if (p->pipe.fold_embed_output && folded_fwd(g)) m.wt0 = wt(p->o_wt0f);
+          if (int rc = launch_tp_mom_bwd_first<T>(p->pipe.chain_pair, m, stream)) return rc;
           if (int rc = mark("tp_mom_bwd_first", p->D + 2 * W + 2 * u + 2 * m.ka0 + 2 * p->D, 2.0 * p->D * u)) return rc;
         }
         continue;
       }
-      if (p->chain_pair >= 0) {
+      if (p->pipe.chain_pair >= 0) {
         TpChainArgs a = chain_args(g);
         a.gscal0 = buf(w.g_scal[0]);
         a.gscal1 = buf(w.g_scal[1]);
@@ -2421,15 +2468,15 @@ struct Runner {
         a.gsh_x1 = buf(w.g_sh);
         a.gsh_env = buf(w.g_sh) + size_t(l + 1) * size_t(E) * p->D;
         if (l == 1) {
-          if (int rc = launch_tp_chain_bwd_last<T>(p->chain_pair, a, stream)) return rc;
+          if (int rc = launch_tp_chain_bwd_last<T>(p->pipe.chain_pair, a, stream)) return rc;
           if (int rc = mark("tp_chain_bwd_last", 3 * W + 2 * p->D + u, 2.0 * p->D * u)) return rc;
         } else {
-          if (int rc = launch_tp_chain_bwd_first<T>(p->chain_pair, a, stream)) return rc;
+          if (int rc = launch_tp_chain_bwd_first<T>(p->pipe.chain_pair, a, stream)) return rc;
           if (int rc = mark("tp_chain_bwd_first", 4 * W + 3 * p->D + 2 * u, 2.0 * p->D * u)) return rc;
         }
         continue;
       }
-      if (p->use_spec) {
+      if (p->pipe.channel_minor()) {
         TpSpecBwdArgs a{};
         a.E = E;
         a.N = N;
@@ -2460,7 +2507,7 @@ struct Runner {
         a.gsh_x1 = buf(w.g_sh);
         a.gsh_env = buf(w.g_sh) + size_t(l + 1) * size_t(E) * p->D;
         a.ld_gsh = p->D;
-        if (int rc = launch_tp_spec_bwd<T>(p->spec_sig[l], a, stream)) return rc;
+        if (int rc = launch_tp_spec_bwd<T>(p->pipe.spec_sig[l], a, stream)) return rc;
         if (int rc = mark("tp_spec_bwd", 4 * W + 3 * p->D + 2 * u * p->D + u, 2.0 * p->D * u)) return rc;
         continue;
       }
@@ -2494,7 +2541,7 @@ struct Runner {
       if (int rc = launch_tp_layer_bwd<T>(p->layers[l], a, stream)) return rc;
       if (int rc = mark("tp_layer_bwd", 4 * W + 2 * p->D + 2 * u * p->D + u, 2.0 * p->D * u)) return rc;
     }
-    if (p->chain_gemm) {
+    if (p->pipe.chains()) {
       // first-stage reverse + scalar_embed_mlp reverse in ONE kernel
       ChainArgs ca{};
       ca.nlayers = 3;
@@ -2506,12 +2553,12 @@ struct Runner {
       ca.L[0] = chain_layer(E, in, 0, wt(p->o_g0tq), p->ng0, S, cn, nullptr, nullptr, &ad, 0, 0, 0);
       ca.L[1] = chain_layer(E, none, 0, wt(p->embed.wtq[1]), S, 64, cn, nullptr, &zz, nullptr, 1, 0, 0);
       ca.L[2] = chain_layer(E, none, 0, wt(p->embed.wtq[0]), 64, c.embed_dim, ce, nullptr, nullptr, nullptr, 1, -1, 0);
-      if (p->o_g0tfq && folded_fwd(g)) {
+      if (p->pipe.fold_embed_output && folded_fwd(g)) {
         // everything in front of the hidden layer of scalar_embed_mlp folded (fold_embed_output; the forward stored a_e, not the embedding):
         // d h = ((d[two-body | w0] @ (W1 G0)^T) + d a_e of the moments) x silu'(h) -- ONE 256 -> 64 layer, 8 steps -- ...
         ca.nlayers = 1;
         ca.L[0] = chain_layer(E, in, 0, wt(p->o_g0tfq), p->ng0, 64, cn, nullptr, &zz, &ad, 0, 0, 0);
-        if (p->embed_fused && p->o_embtab_h) {
+        if (p->pipe.embed_fused && p->pipe.fold_embed_table) {
           // ... contracted against the folded two-body table in its epilogue
           ca.L[0].embrev_out = buf(w.trev);
           ca.emb_table = wt(p->o_embtab_h);
@@ -2524,7 +2571,7 @@ struct Runner {
           ca.nlayers = 2;
           ca.L[1] = chain_layer(E, none, 0, wt(p->embed.wtq[0]), 64, c.embed_dim, ce, nullptr, nullptr, nullptr, 1, -1, 0);
         }
-      } else if (p->embed_fused && p->o_embtab_h) {
+      } else if (p->pipe.embed_fused && p->pipe.fold_embed_table) {
         // folded table (fold_embed_table): d_h, the output of the second layer, is contracted straight back to the 8 basis functions
         // with T = tab @ W0 -- the layer W0^T and d emb0 do not exist
         ca.nlayers = 2;
@@ -2534,7 +2581,7 @@ struct Runner {
         ca.types = g->types;
         ca.center = g->center;
         ca.nbr = g->nbr;
-      } else if (p->embed_fused) {
+      } else if (p->pipe.embed_fused) {
         // d emb0 is contracted straight back to the 8 basis functions in the epilogue and never stored
         ca.L[2].g.c = SegList{1, {seg(nullptr, c.embed_dim, c.embed_dim)}};
         ca.L[2].embrev_out = buf(w.trev);
@@ -2549,12 +2596,12 @@ struct Runner {
     // fused first stage reverse
     {
       SegList go{3, {seg(buf(w.g_fcat), SL1, S), seg(buf(w.g_w0), W, W), seg(buf(w.g_envw), W, W)}};
-      if (p->env_mom) go.count = 2;
+      if (p->pipe.env_moments()) go.count = 2;
       SegList gi{1, {seg(buf(w.g_emb), S, S)}};
-      SegList aenv{1, {seg(p->env_mom ? buf(w.g_aenv) : nullptr, S, S)}};
+      SegList aenv{1, {seg(p->pipe.env_moments() ? buf(w.g_aenv) : nullptr, S, S)}};
       act_now = AA_ACT_SILU;
       if (int rc = gemm(go, 0, wt(p->o_g0t), wt(p->o_g0tp), wt(p->o_g0tq), p->ng0, S, gi, nullptr, nullptr,
-                        p->env_mom ? &aenv : nullptr))
+                        p->pipe.env_moments() ? &aenv : nullptr))
         return rc;
     }
     // scalar_embed_mlp reverse
