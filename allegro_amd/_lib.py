@@ -67,7 +67,7 @@ def options_from_env() -> PlanOptions:
     o.op_recompute_bvecs = flag("AA_OP_RECOMPUTE_BVECS")  # A/B: tp_op_bvecs_kernel in the layer-0 reverse
     o.readout_two_pass = flag("AA_READOUT_TWO_PASS")  # A/B: readout_backward_kernel instead of the fused energy + slope pass
     o.tp_prefer_moments = flag("AA_TP_PREFER_MOM")  # A/B: the round-4 selection (moments kernels) where the operator kernels are now preferred
-    o.fused_narrow = {"1": 1, "2": 2, "3": 3}.get(env.get("AA_FUSED_NARROW", "")[:1], 0)  # A/B: 1 = the one-wave-per-SIMD fused forward, 2 = the eight-wave form (+ tail) at any size, 3 = the four-wave form at any size
+    o.fused_narrow = {"1": 1, "2": 2, "3": 3, "4": 4}.get(env.get("AA_FUSED_NARROW", "")[:1], 0)  # A/B: 1 = the one-wave-per-SIMD fused forward, 2 = the eight-wave form (+ deep tail) at any size, 3 = the four-wave form at any size, 4 = the eight-wave form with the chain-only tail at any size
     o.chain_staged_weights = flag("AA_CHAIN_STAGED")  # A/B: the general chain kernel for the one-layer reverse chains
     o.poison_workspace = flag("AA_POISON")  # debugging: NaN-filled workspace before every step
     o.f64_rows = {"0": 2, "2": 1}.get(env.get("AA_F64_ROWS", "")[:1], 0)  # 0: off, 2: wherever applicable

@@ -711,20 +711,24 @@ struct FusedFwdArgs {
   float* g_fcat;
   float* g_scal1;
   int ld_gfcat;
+  // ... and the deep tail (FusedForm::EightWaveDeepTail): the layer-1 moments reverse and the latent-0 reverse chain behind it -- d EDGE_FEATURES[:, :64],
+  // d scal0, d scal1 and the layer-1 slab of d Y leave the kernel; d EDGE_FEATURES[:, 64:128] and d a_0 of the moments are never written
+  float* g_scal0;   // [E,64]
+  float* gsh_env1;  // [E,D]
 };
 size_t fused_fwd_lds_bytes(int num_types, bool teams);  // dynamic LDS of the fused forward (aa_fused.hip); the CU has 160 KB
 // Form of the one-tile pass of the fused forward (decided once per step by Runner::forward_fused): the one-wave-per-SIMD kernel
 // (aa_fused.hip), or the two-waves-per-SIMD kernel (aa_fused8.hip) as two four-wave workgroups per CU, one eight-wave workgroup per
 // CU, or eight waves with the readout-reverse chain in its tail.  A team pass over the long atoms (mixed form) always runs one wave
 // per SIMD.
-enum class FusedForm { OneWave, FourWave, EightWave, EightWaveTail };
+enum class FusedForm { OneWave, FourWave, EightWave, EightWaveTail, EightWaveDeepTail };
 int fused_fwd_num_steps(int R);
 // `wide` (the same arguments with the weight program of the two-waves-per-SIMD form; set unless `form` is OneWave) takes the one-tile
 // pass (all atoms, or all but the long ones of the mixed form); the team pass keeps `a`
 int launch_fused_fwd(int pair, FusedForm form, const FusedFwdArgs& a, const FusedFwdArgs* wide, hipStream_t stream);
-int fused_fwd8_num_steps(int R, bool tail);
+int fused_fwd8_num_steps(int R, int tail);  // tail: 0 none, 1 the readout-reverse chain, 2 the deep tail
 size_t fused_fwd8_lds_bytes(int num_types, int waves);  // per workgroup of 8 waves (one per CU) or 4 waves (two per CU)
-int launch_fused_fwd8(int pair, FusedForm form, const FusedFwdArgs& a, hipStream_t stream);  // form: FourWave, EightWave or EightWaveTail
+int launch_fused_fwd8(int pair, FusedForm form, const FusedFwdArgs& a, hipStream_t stream);  // form: FourWave, EightWave, EightWaveTail or EightWaveDeepTail
 
 
 // ----------------------------------------------------------------------------------------------

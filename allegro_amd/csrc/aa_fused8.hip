@@ -53,12 +53,13 @@ static_assert(64 * kLdY8 <= 32 * kLdT, "sM must fit the patch");
 // patch: lane (k = lane & 31, half = lane >> 5) walks rows 16 half .. 16 half + 15 of its column; the halves meet through one
 // v_permlane32_swap per component (a = [M0.lo | M1.lo], b = [M0.hi | M1.hi]; a + b: lanes < 32 feature k of tile 0, lanes >= 32
 // feature k of tile 1 = feature `lane` of the pair).  Rows beyond the segment carry Y = 0.
-template <int D>
+// (J0, NJ: only the components J0 .. J0 + NJ - 1 are formed, into M[0 .. NJ - 1] -- the deep tail's moments of one irrep's tile)
+template <int D, int J0 = 0, int NJ = D>
 __device__ __forceinline__ void tile_moments_half(float* sT, const float* sY, const v16f& t0, const v16f& t1, int lane, float* M) {
   const int el = lane & 31, hh = lane >> 5;
-  float M0[D], M1[D];
+  float M0[NJ], M1[NJ];
 #pragma unroll
-  for (int j = 0; j < D; ++j) {
+  for (int j = 0; j < NJ; ++j) {
     M0[j] = 0.f;
     M1[j] = 0.f;
   }
@@ -74,23 +75,74 @@ __device__ __forceinline__ void tile_moments_half(float* sT, const float* sY, co
       const float a = col[i * kLdT];
       float y[12];
 #pragma unroll
-      for (int q = 0; q < (D + 3) / 4; ++q) {
+      for (int q = J0 / 4; q < (J0 + NJ + 3) / 4; ++q) {
         const v4f yy = *reinterpret_cast<const v4f*>(yr + i * kLdY8 + 4 * q);
 #pragma unroll
         for (int c = 0; c < 4; ++c) y[4 * q + c] = yy[c];
       }
 #pragma unroll
-      for (int j = 0; j < D; ++j) Mx[j] += y[j] * a;
+      for (int j = 0; j < NJ; ++j) Mx[j] += y[J0 + j] * a;
     }
     __builtin_amdgcn_wave_barrier();
   };
   pass(t0, M0);
   pass(t1, M1);
 #pragma unroll
-  for (int j = 0; j < D; ++j) {
+  for (int j = 0; j < NJ; ++j) {
     permlane32_swap(M0[j], M1[j]);
     M[j] = M0[j] + M1[j];
   }
+}
+
+// project_moments (aa_fused_tile.h) with the TRANSPOSED env weights in the layout the moments reverse kernels read, Wt[r][ch][k] (64 R rows
+// of 64): out[j] (lane = k) = f * sum_ch g[j][ch] * Wt[r(j)][ch][k].  Step c of the four brings rows 48 c .. 48 c + 47 as one 12-KB
+// window; where 64 R is not a multiple of 48 the last windows start at row 64 R - 48 (inside the matrix) and only their rows from
+// 48 c on are used.  g is handed over through sM [ch][LDY]; every row contributes to the 2 r + 1 components of its irrep.
+template <int S0, int NS, int D, int R, int LDY, class Args, class Pipe>
+__device__ __forceinline__ void project_moments_t(const Args& A, Pipe& p, float* sM, const float* g, float sf, float* out) {
+  const int lane = p.lane;
+#pragma unroll
+  for (int q = 0; q < (D + 3) / 4; ++q) {
+    v4f mm;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) mm[i] = 4 * q + i < D ? g[4 * q + i] : 0.f;
+    *reinterpret_cast<v4f*>(sM + lane * LDY + 4 * q) = mm;
+  }
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int j = 0; j < D; ++j) out[j] = 0.f;
+  static_for<0, 4>([&](auto cc) {
+    constexpr int c = decltype(cc)::value;
+    constexpr int S = S0 + c;
+    constexpr int row0 = 48 * c < 64 * R - 48 ? 48 * c : 64 * R - 48;  // first row of the window (as the host program places it)
+    constexpr int lo = 48 * c, hi = 48 * (c + 1) < 64 * R ? 48 * (c + 1) : 64 * R;
+    pipe_issue<S, NS>(A, p);
+    const float* wf = reinterpret_cast<const float*>(p.wbuf + (S & 1) * kWStep) + lane;
+    static_for<0, 24>([&](auto pp) {  // two rows per region (see project_moments)
+      static_for<0, 2>([&](auto hh2) {
+        constexpr int L = lo + 2 * decltype(pp)::value + decltype(hh2)::value;
+        if constexpr (L < hi) {
+          constexpr int r = L / 64, ch = L % 64, j0 = r * r, nj = 2 * r + 1;
+          const float w = wf[(L - row0) * 64];
+          float m[12];
+#pragma unroll
+          for (int q = j0 / 4; q < (j0 + nj + 3) / 4; ++q) {
+            const v4f mv = *reinterpret_cast<const v4f*>(sM + ch * LDY + 4 * q);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) m[4 * q + i] = mv[i];
+          }
+#pragma unroll
+          for (int j = j0; j < j0 + nj; ++j) out[j] += m[j] * w;
+        }
+      });
+#pragma unroll
+      for (int j = 0; j < D; ++j) anchor(out[j]);
+      __builtin_amdgcn_sched_barrier(0);
+    });
+    pipe_commit<S>(p);
+  });
+#pragma unroll
+  for (int j = 0; j < D; ++j) out[j] *= sf;
 }
 
 // one weight step: the 24 MFMAs of chunk `x` into the accumulator pair, `between` (the split of the next chunk, a parked-tile
@@ -187,7 +239,7 @@ struct TileIn8 {
 
 }  // namespace
 
-constexpr int fused_fwd8_steps(int R, bool tail) { return 4 + (2 + 2 * R) + 4 + 4 + 2 + 8 + 2 + (tail ? 12 : 0); }
+constexpr int fused_fwd8_steps(int R, int tail) { return 4 + (2 + 2 * R) + 4 + 4 + 2 + 8 + 2 + (tail == 2 ? 20 : tail == 1 ? 12 : 0); }  // tail: depth 0 / 1 / 2
 
 // WAVES = 8: one workgroup per CU, eight tiles in lock step (both two-body tiles parked in LDS: 16.6 KB per wave).
 // WAVES = 4: TWO independent workgroups per CU (78 KB of LDS each: one two-body tile parked, the other in 16 registers), each with
@@ -197,9 +249,17 @@ constexpr int fused_fwd8_steps(int R, bool tail) { return 4 + (2 + 2 * R) + 4 + 
 //       silu'(h1); d EDGE_FEATURES[:, :128] = [d ro_h | d h1] W_b; d scal1 = d h1 W_c -- 12 more steps on the same weight fragments the
 //       chain kernel uses) runs here, where its operands are in registers: the total energy is a plain sum, so the gradient seeds of
 //       every edge-local layer are known at the end of the edge's own forward.
-template <class Sig0, class Sig1, int WAVES, bool TAIL>
+// TAIL = 2 (the deep tail): behind that chain, the layer-1 moments reverse (tp_mom_bwd_last_kernel) and the latent-0 reverse chain
+//       (chain_b2_resident_kernel) on the tiles the wave holds -- the edges are center-sorted and the wave owns ALL edges of its atom, so
+//       the per-atom sums of the moments reverse are complete inside the tile.  Q1 = moments of d scal1 * w0_r (w0 from this wave's own
+//       rows, as in the forward's layer-1 scalars); g2 = sf Sig1^T_x2(1, Sig0(Q1, x2s0)); GM = g2 projected with the TRANSPOSED layer-1
+//       env weights (four more projection steps, the matrix tp_mom_bwd_last reads); per edge d a_0 (moments) = Y GM and the layer-1 slab of d Y = a_0 GM; then
+//       (d a_0 [chain, parked instead of stored] + d a_0 [moments]) silu'(h_0) times the 64 x 128 matrix of latent 0's first layer
+//       (four more MFMA steps) -> += d EDGE_FEATURES[:, :64] | d scal0.  d EDGE_FEATURES[:, 64:128] and d a_0 of the moments never exist in HBM.
+template <class Sig0, class Sig1, int WAVES, int TAIL>
 __global__ __launch_bounds__(64 * WAVES, 2) void fused_fwd8_kernel(FusedFwdArgs A) {
   static_assert(WAVES == 8 || WAVES == 4, "workgroup forms");
+  static_assert(TAIL >= 0 && TAIL <= 2 && (TAIL == 0 || WAVES == 8), "the tails exist for the eight-wave form");
   constexpr int NT = 64 * WAVES;                   // threads
   constexpr int NPARK = WAVES == 8 ? 2 : 1;        // parked two-body tiles
   constexpr int kWaveF = kOffPark8 + NPARK * kTileFloats;  // floats of LDS per wave
@@ -208,7 +268,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fused_fwd8_kernel(FusedFwdArgs 
   static_assert(D <= 9, "l_max <= 2");
   constexpr int kPS = 4;  // pipeline steps of one env projection
   constexpr int S_P0 = 0, S_L2 = kPS, S_L3 = S_L2 + 2 + 2 * R, S_P1 = S_L3 + 4, S_L6A = S_P1 + kPS, S_M = S_L6A + 2, S_L8K = S_M + 8, S_T = S_L8K + 2,
-                NS = S_T + (TAIL ? 12 : 0);
+                S_Q = S_T + 12, S_B2 = S_Q + kPS, NS = S_T + (TAIL == 2 ? 12 + kPS + 4 : TAIL == 1 ? 12 : 0);
+  constexpr bool DEEP = TAIL == 2;
   static_assert(NS % 2 == 0 && NS <= kFusedMaxSteps && NS == fused_fwd8_steps(R, TAIL), "program length");
   u32x4* wbuf = reinterpret_cast<u32x4*>(aa_smem);
   float* sRo = reinterpret_cast<float*>(wbuf + 2 * kWStep);  // [64] last readout weights
@@ -547,7 +608,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fused_fwd8_kernel(FusedFwdArgs 
       fused_step8<S_M + 7, NS>(A, p, xs[1], a80, a81, [&] {});
       AA_TICK8(8)
       // latent 1: pre-activation stored, a_1 = silu(h) feeds the readout (its output layer is folded: fold_latent_outputs)
-      if constexpr (TAIL) {  // (the reverse of this layer runs below: its pre-activation is needed there, not in HBM)
+      if constexpr (TAIL != 0) {  // (the reverse of this layer runs below: its pre-activation is needed there, not in HBM)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           dk0[r] = dsilu(a60[r]);
@@ -566,7 +627,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fused_fwd8_kernel(FusedFwdArgs 
     AA_TICK8(9)
     // ---- readout: hidden pre-activation stored; last linear layer + edge sum
     {
-      if constexpr (!TAIL) {
+      if constexpr (TAIL == 0) {
         tile_store_rows8(sW, a80, (A.ro_h) + row0 * 64, cnt, 64, lane);
         tile_store_rows8(sW, a81, (A.ro_h + 32) + row0 * 64, cnt, 64, lane);
       }
@@ -590,7 +651,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fused_fwd8_kernel(FusedFwdArgs 
         A.atom_energy[atom] = en;
       }
     }
-    if constexpr (TAIL) {
+    if constexpr (TAIL != 0) {
       // ---- readout-reverse chain (see TAIL): d ro_h in place of ro_h
       float rofac = A.ro_factor;
       if (A.scales && atom_ok) rofac *= A.scales[A.types[atom]];
@@ -632,14 +693,138 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fused_fwd8_kernel(FusedFwdArgs 
         fused_step8<S_T + 2 + 4 * pr + 1, NS>(A, p, xd[1], t0, t1, [&] {});
         fused_step8<S_T + 2 + 4 * pr + 2, NS>(A, p, xh[0], t0, t1, [&] {});
         fused_step8<S_T + 2 + 4 * pr + 3, NS>(A, p, xh[1], t0, t1, [&] {});
-        tile_store_rows8(sW, t0, (A.g_fcat + 64 * pr) + row0 * A.ld_gfcat, cnt, unsigned(A.ld_gfcat), lane);
-        tile_store_rows8(sW, t1, (A.g_fcat + 64 * pr + 32) + row0 * A.ld_gfcat, cnt, unsigned(A.ld_gfcat), lane);
+        if constexpr (DEEP && pr == 1) {  // (d a_0 of the chain: consumed below, in the slots of the two-body tiles)
+          park_tile(sPark, t0, lane);
+          park_tile(sPark + kTileFloats, t1, lane);
+        } else {
+          tile_store_rows8(sW, t0, (A.g_fcat + 64 * pr) + row0 * A.ld_gfcat, cnt, unsigned(A.ld_gfcat), lane);
+          tile_store_rows8(sW, t1, (A.g_fcat + 64 * pr + 32) + row0 * A.ld_gfcat, cnt, unsigned(A.ld_gfcat), lane);
+        }
       });
       zero();  // d scal1 = d h1 @ W_c
       fused_step8<S_T + 10, NS>(A, p, xh[0], t0, t1, [&] {});
       fused_step8<S_T + 11, NS>(A, p, xh[1], t0, t1, [&] {});
       tile_store_rows8(sW, t0, (A.g_scal1) + row0 * 64, cnt, 64, lane);
       tile_store_rows8(sW, t1, (A.g_scal1 + 32) + row0 * 64, cnt, 64, lane);
+      if constexpr (DEEP) {
+        // ---- layer-1 moments reverse (see TAIL = 2): Q1[i] (lane = channel) = sum_e d scal1[e] * Y[e][i] * w0[e][r(i)]
+        float GM[D];
+        {
+          float q1[D];
+          v16f wa = tile_load_rows8(A.w0 + row0 * (64 * R), 64 * R, lane, row_ok), wb = tile_load_rows8(A.w0 + row0 * (64 * R) + 32, 64 * R, lane, row_ok);
+          static_for<0, R>([&](auto rr) {
+            constexpr int r = decltype(rr)::value;
+            v16f na = wa, nb = wb;
+            if constexpr (r + 1 < R) {
+              na = tile_load_rows8(A.w0 + row0 * (64 * R) + (r + 1) * 64, 64 * R, lane, row_ok);
+              nb = tile_load_rows8(A.w0 + row0 * (64 * R) + (r + 1) * 64 + 32, 64 * R, lane, row_ok);
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+              wa[i] *= t0[i];
+              wb[i] *= t1[i];
+            }
+            tile_moments_half<D, r * r, 2 * r + 1>(sW, sY, wa, wb, lane, q1 + r * r);
+            wa = na;
+            wb = nb;
+          });
+          // per atom: g2 = d x2s1 = sf Sig1^T_x2(1, Sig0(Q1, x2s0)) (the contractions of tp_mom_bwd_last_kernel)
+          float wp0[Sig0::P], wp1[Sig1::P];
+#pragma unroll
+          for (int q = 0; q < Sig0::P; ++q) wp0[q] = load_pw(A.tpw0, Sig0::P, q);
+#pragma unroll
+          for (int q = 0; q < Sig1::P; ++q) wp1[q] = load_pw(A.tpw1, Sig1::P, q);
+          float x2s0b[D], tq[D], g2[D], one[1] = {1.f};
+#pragma unroll
+          for (int j = 0; j < D; ++j) x2s0b[j] = atom_ok ? *at_bytes(A.x2s0 + (atom * D + j) * 64, 4u * unsigned(lane)) : 0.f;
+          Sig0::template fwd<float>(q1, x2s0b, wp0, tq);
+          Sig1::template bx2<float>(one, tq, wp1, g2);
+          // GM[j] (lane = k) = sf sum_ch g2[j][ch] Wenv1[k][r(j)][ch]: the forward's projection, on the transposed weights
+          project_moments_t<S_Q, NS, D, R, kLdY8>(A, p, sW, g2, A.sf, GM);
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int a = 0; a < D; ++a) sBv[a * 64 + lane] = GM[a];
+        __builtin_amdgcn_wave_barrier();
+        // per edge: d a_0 (moments) = sum_j Y[j] GM[j][k] (tile); d Y[j] (layer-1 slab) = sum_k a_0[k] GM[j][k], a_0 = silu(h_0) with h_0
+        // from this wave's own rows
+        v16f h0a = tile_load_rows8(A.lat_h0 + row0 * 64, 64, lane, row_ok), h0b = tile_load_rows8(A.lat_h0 + row0 * 64 + 32, 64, lane, row_ok);
+        {
+          float Yv[D], gy[D];
+          load_Y(Yv);
+#pragma unroll
+          for (int a = 0; a < D; ++a) gy[a] = 0.f;
+          const float* bb = sBv + 4 * hh;
+#pragma unroll
+          for (int g = 0; g < 8; ++g) {
+            const int q = g & 3;
+            v4f T4 = {0.f, 0.f, 0.f, 0.f}, av;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) av[i] = silu(g < 4 ? h0a[4 * q + i] : h0b[4 * q + i]);
+#pragma unroll
+            for (int a = 0; a < D; ++a) {
+              const v4f b = *reinterpret_cast<const v4f*>(bb + a * 64 + 32 * (g >> 2) + 8 * q);
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                T4[i] += Yv[a] * b[i];
+                gy[a] += av[i] * b[i];
+              }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              if (g < 4)
+                t0[4 * q + i] = T4[i];
+              else
+                t1[4 * q + i] = T4[i];
+            }
+            if (g < 4)
+              anchor(t0);
+            else
+              anchor(t1);
+#pragma unroll
+            for (int a = 0; a < D; ++a) anchor(gy[a]);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+#pragma unroll
+          for (int a = 0; a < D; ++a) gy[a] += __shfl_xor(gy[a], 32);
+          if (row_ok && hh == 0) {
+            float* gb = A.gsh_env1 + row0 * D;
+#pragma unroll
+            for (int m = 0; m < D; ++m) *at_bytes(gb, 4u * (unsigned(el) * D + m)) = gy[m];
+          }
+        }
+        // ---- latent-0 reverse: (d a_0 [chain] + d a_0 [moments]) silu'(h_0) @ W -> [+= d EDGE_FEATURES[:, :64] | d scal0]
+        XSplit xo[2];
+        {
+          v16f da = fetch_tile(sPark, lane);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) t0[r] = (da[r] + t0[r]) * dsilu(h0a[r]);
+          da = fetch_tile(sPark + kTileFloats, lane);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) t1[r] = (da[r] + t1[r]) * dsilu(h0b[r]);
+          xsplit_from_acc(t0, xo[0]);
+          xsplit_from_acc(t1, xo[1]);
+        }
+        zero();
+        fused_step8<S_B2 + 0, NS>(A, p, xo[0], t0, t1, [&] {});
+        fused_step8<S_B2 + 1, NS>(A, p, xo[1], t0, t1, [&] {});
+        {  // (the chain's share of these columns: this wave's own store above)
+          const v16f oa = tile_load_rows8(A.g_fcat + row0 * A.ld_gfcat, unsigned(A.ld_gfcat), lane, row_ok);
+          const v16f ob = tile_load_rows8(A.g_fcat + row0 * A.ld_gfcat + 32, unsigned(A.ld_gfcat), lane, row_ok);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            t0[r] += oa[r];
+            t1[r] += ob[r];
+          }
+        }
+        tile_store_rows8(sW, t0, (A.g_fcat) + row0 * A.ld_gfcat, cnt, unsigned(A.ld_gfcat), lane);
+        tile_store_rows8(sW, t1, (A.g_fcat + 32) + row0 * A.ld_gfcat, cnt, unsigned(A.ld_gfcat), lane);
+        zero();
+        fused_step8<S_B2 + 2, NS>(A, p, xo[0], t0, t1, [&] {});
+        fused_step8<S_B2 + 3, NS>(A, p, xo[1], t0, t1, [&] {});
+        tile_store_rows8(sW, t0, (A.g_scal0) + row0 * 64, cnt, 64, lane);
+        tile_store_rows8(sW, t1, (A.g_scal0 + 32) + row0 * 64, cnt, 64, lane);
+      }
     }
     AA_TICK8(10)
     cur.beg = nxt.beg;
@@ -664,19 +849,20 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fused_fwd8_kernel(FusedFwdArgs 
 size_t fused_fwd8_lds_bytes(int num_types, int waves) {
   return sizeof(u32x4) * 2 * kWStep + sizeof(float) * (64 + 32 + size_t(num_types) * num_types * 512 + size_t(waves) * fused_wave_floats(waves));
 }
-int fused_fwd8_num_steps(int R, bool tail) { return fused_fwd8_steps(R, tail); }
+int fused_fwd8_num_steps(int R, int tail) { return fused_fwd8_steps(R, tail); }
 
 int launch_fused_fwd8(int pair, FusedForm form, const FusedFwdArgs& a, hipStream_t stream) {
   if (a.atom_end <= a.atom0) return AA_OK;
   if (form == FusedForm::OneWave) return fail(AA_ERR_INVALID, "fused forward (wide): 4 or 8 waves per workgroup");
   const int waves = form == FusedForm::FourWave ? 4 : 8;
-  const bool tail = form == FusedForm::EightWaveTail;
+  const int tail = form == FusedForm::EightWaveDeepTail ? 2 : form == FusedForm::EightWaveTail ? 1 : 0;
   const size_t smem = fused_fwd8_lds_bytes(a.num_types, waves);
   if (smem * (waves == 4 ? 2 : 1) > 160 * 1024) return fail(AA_ERR_INVALID, "fused forward (wide): LDS budget exceeded");
   if (!a.w0) return fail(AA_ERR_INVALID, "fused forward (wide): needs the w0 rows");
   // (the tail exists for the eight-wave form: with four-wave workgroups -- 24 instead of 16 staging registers, one two-body tile in
   //  registers -- it spills 186 registers and the kernel takes 5.1-5.3 instead of 4.3 ms at C4, profiles/r06_v19_*)
   if (tail && (!a.g_fcat || !a.g_scal1)) return fail(AA_ERR_INVALID, "fused forward (wide): the reverse tail needs its gradient outputs");
+  if (tail == 2 && (!a.g_scal0 || !a.gsh_env1)) return fail(AA_ERR_INVALID, "fused forward (wide): the deep tail needs its gradient outputs");
   const int cus = device_cu_count();
   if (cus < 0) return cus;
   const int64_t ngroups = (a.atom_end - a.atom0 + waves - 1) / waves;
@@ -688,7 +874,7 @@ int launch_fused_fwd8(int pair, FusedForm form, const FusedFwdArgs& a, hipStream
     hipLaunchKernelGGL((fused_fwd8_kernel<cg::S0_, cg::S1_, W_, T_>), grid, dim3(64 * W_), smem, stream, a);  \
   }
 #define AA_FUSED8_LAUNCH(S0_, S1_) \
-  if (tail) AA_FUSED8_LAUNCH1(S0_, S1_, 8, true) else if (waves == 8) AA_FUSED8_LAUNCH1(S0_, S1_, 8, false) else AA_FUSED8_LAUNCH1(S0_, S1_, 4, false)
+  if (tail == 2) AA_FUSED8_LAUNCH1(S0_, S1_, 8, 2) else if (tail == 1) AA_FUSED8_LAUNCH1(S0_, S1_, 8, 1) else if (waves == 8) AA_FUSED8_LAUNCH1(S0_, S1_, 8, 0) else AA_FUSED8_LAUNCH1(S0_, S1_, 4, 0)
   if (pair == 0) {
     AA_FUSED8_LAUNCH(Sig1, Sig0)
   } else if (pair == 1) {

@@ -1399,7 +1399,8 @@ struct Runner {
   StageProfile* prof = nullptr;
   bool want_forces = false;    // (set by run_model before forward())
   bool ro_grad_done = false;   // forward(): readout_reduce also wrote d E / d (last readout hidden layer) -- no readout_backward launch
-  bool fwd_b3_done = false;    // forward_fused(): the readout-reverse chain ran in the tail of the fused forward (FusedForm::EightWaveTail)
+  bool fwd_b3_done = false;    // forward_fused(): the readout-reverse chain ran in the tail of the fused forward (FusedForm::EightWaveTail, EightWaveDeepTail)
+  bool fwd_b2_done = false;    // ... and behind it the layer-1 moments reverse and the latent-0 reverse chain (FusedForm::EightWaveDeepTail)
 
   // per_edge / per_atom: operand elements the launch must move (each distinct operand row once); see DESIGN.md §5
   int mark(const char* name, double per_edge = 0, double per_atom = 0, double flops = 0) {
@@ -1857,7 +1858,10 @@ struct Runner {
   //     that applies (forces requested, no team pass -- its atoms would miss it -- and the chain's folded weights): there the eight-wave
   //     form is as fast as two four-wave workgroups and the chain's 0.75 ms of streaming disappear (C4 -0.45 ms same box,
   //     profiles/r06_v19_*).  Otherwise two four-wave workgroups per CU.
-  //  2: eight waves at any size, with the tail where it applies;  3: four waves at any size, no tail;  1: never (fused_wide is off).
+  //     Where the resident latent-0 chain would run behind it (fold_lat0_reverse, fp32, S = u = latent width = 64) the tail is the DEEP
+  //     one: the layer-1 moments reverse and that chain run in it too, and Runner::backward skips both launches (fwd_b2_done).
+  //  2: eight waves at any size, with the (deep) tail where it applies;  3: four waves at any size, no tail;  1: never (fused_wide is off);
+  //  4: eight waves at any size with the chain-only tail where a tail applies (A/B of the deep tail).
   int fused_form(const FusedFwdArgs& a, FusedForm* form) const {
     *form = FusedForm::OneWave;
     const bool teams = a.tile_atoms != nullptr;
@@ -1866,12 +1870,15 @@ struct Runner {
     if (cus < 0) return cus;
     const int64_t n = a.atom_end - a.atom0;
     const bool tail_ok = want_forces && !teams && p->pipe.chains() && p->pipe.fold_latent_outputs && p->cfg.num_layers == 2;
-    if (p->opt.fused_narrow == 2) {
-      *form = tail_ok ? FusedForm::EightWaveTail : FusedForm::EightWave;
+    const bool deep_ok = tail_ok && p->pipe.fold_lat0_reverse && p->pipe.env_moments() && sizeof(T) == 4 && p->cfg.num_scalar == 64 &&
+                         p->cfg.num_tensor == 64 && p->cfg.latent_mlp_width == 64 && p->opt.fused_narrow != 4;
+    const FusedForm tail_form = deep_ok ? FusedForm::EightWaveDeepTail : FusedForm::EightWaveTail;
+    if (p->opt.fused_narrow == 2 || p->opt.fused_narrow == 4) {
+      *form = tail_ok ? tail_form : FusedForm::EightWave;
     } else if (p->opt.fused_narrow == 3) {
       *form = FusedForm::FourWave;
     } else if (n > int64_t(4) * cus) {
-      *form = tail_ok && n >= int64_t(kFusedTailAtomsPerCu) * cus ? FusedForm::EightWaveTail : FusedForm::FourWave;
+      *form = tail_ok && n >= int64_t(kFusedTailAtomsPerCu) * cus ? tail_form : FusedForm::FourWave;
     }
     return AA_OK;
   }
@@ -1985,7 +1992,8 @@ struct Runner {
       }
       add_step(wf(p->o_ro0_fq), 6, 4);
       add_step(wf(p->o_ro0_fq), 6, 5);
-      const bool tail = form == FusedForm::EightWaveTail;
+      const bool deep = form == FusedForm::EightWaveDeepTail;
+      const bool tail = deep || form == FusedForm::EightWaveTail;
       if (tail) {
         add_layer(wf(p->o_b3af_q), 2, 0, 2);
         add_layer(wf(p->pipe.fold_lat0_reverse ? p->o_b3bf_q : p->o_b3b_q), 4, 0, 4);
@@ -1994,11 +2002,25 @@ struct Runner {
         a8.ld_gfcat = p->SL1;
         a8.g_scal1 = bf(w.g_scal[1]);
       }
-      if (ns != fused_fwd8_num_steps(p->R, tail)) return fail(AA_ERR_INVALID, "fused forward (wide): program length mismatch");
+      if (deep) {  // + the transposed layer-1 env weights [R][u][64] as they are packed for tp_mom_bwd_last -- four windows of 48 of their
+                   //   64 R rows, the last one(s) pulled back inside the matrix (fused_fwd8_kernel: project_moments_t) -- and the first
+                   //   layer of latent 0, transposed (the resident chain's bytes)
+        for (int cblk = 0; cblk < 4; ++cblk) {
+          const int row0 = std::min(48 * cblk, 64 * p->R - 48);
+          prog->wstep[ns][0] = wf(p->o_wt[1]) + size_t(row0) * 64;
+          prog->wstep[ns][1] = wf(p->o_wt[1]) + size_t(row0) * 64 + 1536;
+          ++ns;
+        }
+        add_layer(wf(p->latent[0].wtq[0]), 2, 0, 4);
+        a8.g_scal0 = bf(w.g_scal[0]);
+        a8.gsh_env1 = bf(w.g_sh) + size_t(2) * size_t(E) * p->D;
+      }
+      if (ns != fused_fwd8_num_steps(p->R, deep ? 2 : tail ? 1 : 0)) return fail(AA_ERR_INVALID, "fused forward (wide): program length mismatch");
     }
     if (int rc = mark("begin")) return rc;
     if (int rc = launch_fused_fwd(p->pipe.chain_pair, form, a, form != FusedForm::OneWave ? &a8 : nullptr, stream)) return rc;
-    fwd_b3_done = form == FusedForm::EightWaveTail && a.atom_end > a.atom0;  // (an empty block launches nothing)
+    fwd_b2_done = form == FusedForm::EightWaveDeepTail && a.atom_end > a.atom0;  // (an empty block launches nothing)
+    fwd_b3_done = (fwd_b2_done || form == FusedForm::EightWaveTail) && a.atom_end > a.atom0;
     // algorithmic traffic: neighbor id + shift in; unit vector, harmonics, five 64-wide rows and w0 out per edge;
     // position, two x2s blocks, energy, row pointer per atom.  Flops: the linear layers of the forward (w0 counted once).
     const double per_edge = 1 + (g->shift_vec ? 3 : 0) + 3 + 4 + p->D + 5 * 64 + p->W;
@@ -2006,6 +2028,10 @@ struct Runner {
     double fl = 2.0 * double(E) * (2.0 * 64 * 64 + 64.0 * p->ng0 + double(S + u) * 64 + 64.0 * S + double(2 * S + u) * 64 + 64.0 * S + 3.0 * S * 64);
     if (fwd_b3_done) {  // (+ the readout-reverse chain: 192 gradient columns out instead of two 64-wide pre-activation rows)
       fl += 2.0 * double(E) * (64.0 * 64 + 128.0 * 128 + 64.0 * 64);
+      if (fwd_b2_done) {  // (+ the latent-0 reverse layer; out: d EDGE_FEATURES[:, :64], d scal0, d scal1, d Y instead of 192 columns; lat_h0 read again)
+        fl += 2.0 * double(E) * 64.0 * 128;
+        return mark("fused_fwd", per_edge + 64 + 64 + p->D, per_atom, fl);
+      }
       return mark("fused_fwd", per_edge + 64, per_atom, fl);
     }
     return mark("fused_fwd", per_edge, per_atom, fl);
@@ -2387,6 +2413,7 @@ struct Runner {
         int acc1[3] = {1, 0, 0};
         ca.L[0] = chain_layer(E, in, 0, wt(p->latent[l].wtq[1]), S, 64, cn, nullptr, &zz, &ad, 0, 0, 0);
         ca.L[1] = chain_layer(E, none, 0, wt(p->latent[l].wtq[0]), 64, S * (l + 1) + u, c1, acc1, nullptr, nullptr, 1, -1, 0);
+        if (fwd_b2_done && l == 0) goto b2_done;  // (ran in the deep tail of the fused forward)
         if (p->pipe.fold_lat0_reverse && L == 2 && l == 0) {
           // the readout-reverse chain already applied Wout_0^T (folded into its lat0 columns): what is left of the output layer's
           // reverse is elementwise -- d h = (d a_0 + d a_0 of the moments) x silu'(h) -- and rides as the operand transform of the
@@ -2445,7 +2472,9 @@ struct Runner {
         m.c.gsh_x1 = buf(w.g_sh);
         m.c.gsh_env = buf(w.g_sh) + size_t(l + 1) * size_t(E) * p->D;
         m.g_a = buf(w.g_aenv);
-        if (l == 1) {
+        if (l == 1 && fwd_b2_done) {
+          // (ran in the deep tail of the fused forward: the layer-1 slab of d Y is in the workspace, d a_0 was consumed there)
+        } else if (l == 1) {
           m.ld_ga = c.latent_mlp_width;
           if (int rc = launch_tp_mom_bwd_last<T>(p->pipe.chain_pair, m, stream)) return rc;
           if (int rc = mark("tp_mom_bwd_last", p->D + W + u + 2 * m.ka1 + p->D, double(p->D) * u)) return rc;

@@ -304,9 +304,11 @@ typedef struct {
   int32_t fused_narrow;     /* fused forward, one-tile pass, where the two-waves-per-SIMD form applies (aa_fused8.hip: one species):
                              * 0 = automatic: boxes of at most 4 atoms per CU take the one-wave-per-SIMD kernel (every CU holds at most one
                              * workgroup anyway), from 64 atoms per CU on one eight-wave workgroup per CU with the readout-reverse chain in its
-                             * tail (forces requested, no team pass), else two independent four-wave workgroups per CU; 1 = the
-                             * one-wave-per-SIMD kernel of rounds 2-5 (A/B, tests); 2 = the eight-wave form at any size, with the tail where
-                             * it applies (tests); 3 = the four-wave form at any size, no tail (tests) */
+                             * tail (forces requested, no team pass) -- the deep tail, with the layer-1 moments reverse and the latent-0 reverse chain behind
+                             * it, where the resident latent-0 chain would run --, else two independent four-wave workgroups per CU; 1 = the
+                             * one-wave-per-SIMD kernel of rounds 2-5 (A/B, tests); 2 = the eight-wave form at any size, with the (deep) tail
+                             * where it applies (tests); 3 = the four-wave form at any size, no tail (tests); 4 = the eight-wave form at any
+                             * size with the chain-only tail where a tail applies (A/B of the deep tail) */
   int32_t chain_staged_weights; /* one-layer reverse chains: 1 = the per-workgroup weight staging of the general chain kernel also where the
                                  * persistent form with LDS-resident weights applies (round 6; A/B, tests)                               */
 } aa_plan_options;
