@@ -339,6 +339,171 @@ static ModelPipeline choose_pipeline(const aa_model_config& q, const aa_plan_opt
 }
 
 // ------------------------------------------------------------------------------------------------
+// step plan: which launches ONE step consists of, decided once per step (choose_step)
+// ------------------------------------------------------------------------------------------------
+// What the plan cannot say, because it also depends on the graph of this step, on whether forces were asked for, on the debug
+// taps and on the device.  run_model fills StepInputs from its arguments, choose_step turns them into one StepPlan, and Runner
+// only reads that value: the forward and the reverse pass cannot disagree about what the other one did.
+struct StepInputs {
+  bool f32;                 // dtype of the plan
+  bool taps;                // aa_model_plan_enable_taps: every tap is materialised
+  bool with_forces;
+  bool transposed_csr;      // aa_graph::t_rowptr / t_perm are present
+  int64_t atoms, edges;     // of the graph
+  int64_t atom0, atom_end;  // the active block: the atom-block hint, or every atom
+  int64_t max_degree;       // aa_graph::max_degree, 0 = unknown
+};
+
+enum class ForwardKind {
+  Staged,        // one launch per stage
+  StagedFolded,  // ... with the chains in the folded form of the fused forward (a_e / a_0 stored where the embedding / lat_0 used to be)
+  FusedOneTile,  // ONE kernel, every segment in one 32-edge tile (aa_fused.hip / aa_fused8.hip)
+  FusedTeam,     // ONE kernel, teams of 1 / 2 / 4 waves per atom for every atom
+  FusedMixed,    // one-tile pass over all atoms (the long ones skipped) + team pass over the long ones
+};
+// Reverse stages the forward of this step already ran, as a depth (the values are the `tail` of fused_fwd8_num_steps)
+enum class ReverseInForward {
+  None = 0,
+  Chain = 1,                // the readout-reverse chain (FusedForm::EightWaveTail)
+  ChainMomentsLatent0 = 2,  // ... and behind it the layer-1 moments reverse and the latent-0 reverse chain (FusedForm::EightWaveDeepTail)
+};
+// Form of the reverse of the latent MLPs below the last one (the last one's rides in the readout-reverse chain where there are chains)
+enum class LatentReverse {
+  Mlp,            // mlp_bwd: one launch per layer (every plan without the chains)
+  TwoLayerChain,  // output layer + first layer in one chain kernel
+  FoldedChain,    // fold_lat0_reverse: ONE layer behind the operand transform, general chain kernel
+  Resident,       // ... with its weights resident in LDS (aa_chain_res.hip)
+  InForwardTail,  // ran in the deep tail of the fused forward
+};
+
+struct StepPlan {
+  ForwardKind forward;
+  FusedForm fused_form;                 // fused forwards: form of the one-tile pass (OneWave where there is none)
+  bool slot;                            // slot form of the single-layer pipeline (LinearPath::Slot): forward stages and backward_slot
+  bool op_split;                        // operator kernels: per-atom vectors through HBM, edge loops in lean kernels (off: tp_operator_fused)
+  bool op_split_reverse;                // ... the moment gradients of the reverse too (a force step's workspace holds them)
+  bool proj_forward, proj_reverse;      // operator kernels: the env projections as batched linear-layer launches (ModelPipeline::op_proj)
+  bool readout_grad_in_reduce;          // readout_reduce also writes d E / d (last readout hidden layer): no readout_backward launch
+  ReverseInForward reverse_in_forward;  // the reverse pass launches none of these
+  LatentReverse latent_reverse;
+  bool gather;                          // deterministic force assembly over the transposed CSR (off: atomics)
+  bool zero_gsh, zero_forces;           // the reverse pass accumulates into d Y / the forces: zeroed first
+
+  bool fused() const { return forward == ForwardKind::FusedOneTile || forward == ForwardKind::FusedTeam || forward == ForwardKind::FusedMixed; }
+  // did the forward of this step leave a_e in the embedding's slot (folded first stage / env weights in the reverse)?
+  bool folded_first_stage() const { return forward != ForwardKind::Staged; }
+};
+
+static ReverseInForward fused_tail(FusedForm form) {
+  return form == FusedForm::EightWaveDeepTail ? ReverseInForward::ChainMomentsLatent0
+         : form == FusedForm::EightWaveTail   ? ReverseInForward::Chain
+                                              : ReverseInForward::None;
+}
+
+static ForwardKind choose_forward(const ModelPipeline& pipe, const aa_plan_options& opt, const aa_model_config& c, const StepInputs& in) {
+  // the staged forward chains in the same folded form as the fused forward (fold_embed_output, fold_latent_outputs): the hidden activations a_e /
+  // a_0 are stored where the embedding / lat_0 used to be (ChainLayer::kept_out), consumers run on the folded matrices.  What
+  // graphs with long segments -- dense systems, too large for the team form -- run.
+  const bool fold_staged = pipe.chains() && pipe.tp_op < 0 && pipe.fold_embed_output && pipe.fold_latent_outputs && c.num_layers == 2 && !in.taps &&
+                           !opt.staged_no_fold;
+  const ForwardKind staged = fold_staged ? ForwardKind::StagedFolded : ForwardKind::Staged;
+  // the whole forward in one launch (aa_fused.hip): every center atom's edge segment fits one 32-row MFMA tile
+  if (!(in.f32 && pipe.fused_fwd && !in.taps && in.max_degree > 0 && in.max_degree <= kFusedMaxDegree)) return staged;
+  const bool long_segments = in.max_degree > 32;
+  // (three species + the team exchange area exceed the 160 KB of LDS: such graphs run the staged pipeline)
+  if (fused_fwd_lds_bytes(c.num_types, long_segments) > size_t(160) * 1024) return staged;
+  if (!long_segments) return ForwardKind::FusedOneTile;  // one full-ish tile per atom: faster than the staged forward at every size
+  // Team form (2 / 4 tiles per atom): a tile costs the same whether 32 or 12 of its rows carry an edge, so it pays where
+  // the step is latency-bound (few tiles: one launch instead of seven) or the tiles are nearly full.  Measured on Si boxes
+  // at r_max 6 / 7 (44 / 73 edges per atom, profiles/archive/r03_p_*): 216-512 atoms 17-27 % faster than the staged step, 1 728
+  // atoms -2 % / +8 %, 10 648 atoms +10 % / +18 % slower (69 % / 57 % of the tile rows in use).
+  // (in.edges IS the edge count of the active block: the atom-block hint promises that every center with edges lies in
+  // [atom_begin, atom_end) -- verified on the device by graph_hint_check_kernel -- so rowptr[atom_end] - rowptr[atom_begin],
+  // which the host does not hold, equals aa_graph::num_edges)
+  const int64_t n_active = in.atom_end - in.atom0;
+  const int64_t tiles = n_active * (in.max_degree <= 64 ? 2 : 4);  // (upper bound: every atom at the class of the longest segment)
+  const double fill = double(in.edges) / (32.0 * double(std::max<int64_t>(n_active, 1)));
+  const bool avg_fits_one_tile = fill <= 1.15;
+  // mixed form (one-tile pass over all atoms + team pass over the long ones) where long atoms are the minority -- boxes whose
+  // average atom fits one tile; dense boxes that took the team path because they are small or their tiles are full run the pure
+  // team form: there the one-tile launch would only skip.  2 / 4: the team / mixed form for every graph (A/B)
+  const ForwardKind team = opt.fused_forward == 2 ? ForwardKind::FusedTeam
+                           : (opt.fused_forward == 4 || avg_fits_one_tile) ? ForwardKind::FusedMixed
+                                                                           : ForwardKind::FusedTeam;
+  if (opt.fused_forward == 2 || opt.fused_forward == 4) return team;  // (A/B: the team / mixed form whenever segments fit it)
+  // Round 5: a box whose AVERAGE atom fills most of one tile but whose longest segment is a little over 32 (thermal disorder: a
+  // handful of Si atoms with 33..37 neighbours after 50 fs at 300 K) takes the MIXED form -- one-tile kernel over all atoms, the
+  // team kernel over the long ones only (launch_fused_fwd) -- instead of giving up the fused forward for the whole box
+  // (tools/md_loop.py at C4: staged 11.3 ms, team form for every atom 12.2 ms per step; profiles/r05_v2*_md_loop_*).
+  if (fill >= 0.6 && avg_fits_one_tile) return team;
+  return (tiles <= kFusedTeamTilesSmall || double(in.edges) >= 0.85 * 32.0 * double(tiles)) ? team : staged;
+}
+
+// The two-waves-per-SIMD forms (aa_fused8.hip) need a plan with fused_wide and a one-tile pass (no class lists, or the mixed
+// form); they are the forms whose choice reads the CU count
+static bool wide_one_tile_pass(const ModelPipeline& pipe, ForwardKind forward) {
+  return pipe.fused_wide && (forward == ForwardKind::FusedOneTile || forward == ForwardKind::FusedMixed);
+}
+
+// The whole per-step decision, from the plan (`pipe`, `opt`, `c`: the configuration at the widened sizes), the step's inputs and
+// the CU count of the device (read only where wide_one_tile_pass says so) alone: no HIP call, no allocation.
+static StepPlan choose_step(const ModelPipeline& pipe, const aa_plan_options& opt, const aa_model_config& c, const StepInputs& in, int cus) {
+  const int64_t n = in.atom_end - in.atom0;
+  const bool two_layer_chains = pipe.chains() && c.num_layers == 2;
+  StepPlan s{};
+  s.forward = choose_forward(pipe, opt, c, in);
+
+  // ---- form of the one-tile pass of the fused forward (FusedForm), decided here only.  aa_plan_options.fused_narrow:
+  //  0: boxes that leave a CU at most one workgroup (n <= 4 per CU) run one wave per SIMD whatever the kernel: there the
+  //     register-rich one-wave form -- w0 held, operands kept split -- is the faster one (64 atoms 44 vs 48 us, profiles/r06_v4_ab_c2_*).
+  //     From kFusedTailAtomsPerCu atoms per CU on, eight waves with the readout-reverse chain of the reverse pass in the tail, where
+  //     that applies (forces requested, no team pass -- its atoms would miss it -- and the chain's folded weights): there the eight-wave
+  //     form is as fast as two four-wave workgroups and the chain's 0.75 ms of streaming disappear (C4 -0.45 ms same box,
+  //     profiles/r06_v19_*).  Otherwise two four-wave workgroups per CU.
+  //     Where the resident latent-0 chain would run behind it (fold_lat0_reverse, fp32, S = u = latent width = 64) the tail is the DEEP
+  //     one: the layer-1 moments reverse and that chain run in it too, and the reverse pass skips both launches (reverse_in_forward).
+  //  2: eight waves at any size, with the (deep) tail where it applies;  3: four waves at any size, no tail;  1: never (fused_wide is off);
+  //  4: eight waves at any size with the chain-only tail where a tail applies (A/B of the deep tail).
+  const bool resident_shape = in.f32 && c.num_scalar == 64 && c.num_tensor == 64;  // (what aa_chain_res.hip and the deep tail are written for)
+  const bool tail_ok = in.with_forces && s.forward == ForwardKind::FusedOneTile && two_layer_chains && pipe.fold_latent_outputs;
+  const bool deep_ok = tail_ok && pipe.fold_lat0_reverse && pipe.env_moments() && resident_shape && c.latent_mlp_width == 64 && opt.fused_narrow != 4;
+  const FusedForm tail_form = deep_ok ? FusedForm::EightWaveDeepTail : FusedForm::EightWaveTail;
+  s.fused_form = !wide_one_tile_pass(pipe, s.forward)                ? FusedForm::OneWave
+                 : (opt.fused_narrow == 2 || opt.fused_narrow == 4) ? (tail_ok ? tail_form : FusedForm::EightWave)
+                 : opt.fused_narrow == 3                             ? FusedForm::FourWave
+                 : n <= int64_t(4) * cus                             ? FusedForm::OneWave
+                 : (tail_ok && n >= int64_t(kFusedTailAtomsPerCu) * cus) ? tail_form
+                                                                         : FusedForm::FourWave;
+  s.reverse_in_forward = n > 0 ? fused_tail(s.fused_form) : ReverseInForward::None;  // (an empty block launches nothing)
+
+  // ---- linear layers ----
+  // slot form of the single-layer pipeline (LinearPath::Slot); the debug taps name tensors it never forms
+  s.slot = pipe.slot() && !in.taps;
+  s.readout_grad_in_reduce = in.with_forces && !pipe.chains() && c.readout_mlp_depth > 0 && !opt.readout_two_pass;
+  s.latent_reverse = !pipe.chains()                                                     ? LatentReverse::Mlp
+                     : s.reverse_in_forward == ReverseInForward::ChainMomentsLatent0 ? LatentReverse::InForwardTail
+                     : !(pipe.fold_lat0_reverse && c.num_layers == 2)                ? LatentReverse::TwoLayerChain
+                     : (resident_shape && !opt.chain_staged_weights)                 ? LatentReverse::Resident
+                                                                                     : LatentReverse::FoldedChain;
+
+  // ---- operator kernels ----
+  // split form (default): per-atom vectors through HBM, edge loops in lean kernels (tp_operator_fused: fused form)
+  s.op_split = pipe.tp_op >= 0 && !opt.tp_operator_fused;
+  s.op_split_reverse = s.op_split && in.with_forces;
+  // env projections of the operator kernels as batched linear-layer launches (ModelPipeline::op_proj): where there are enough
+  // atoms to fill the chip with 128-row tiles
+  s.proj_forward = pipe.op_proj && s.op_split && (opt.op_proj_gemm == 1 || n >= 4096);
+  s.proj_reverse = s.proj_forward && in.with_forces;
+
+  // ---- what the reverse pass sums into ----
+  s.gather = in.transposed_csr;
+  // spec path with u <= 64 writes every g_sh slot with plain stores; otherwise slots are accumulated into
+  s.zero_gsh = in.with_forces && !((pipe.channel_minor() && c.num_tensor <= 64) || pipe.tp_op >= 0);
+  s.zero_forces = in.with_forces && !s.gather;
+  return s;
+}
+
+// ------------------------------------------------------------------------------------------------
 // model plan
 // ------------------------------------------------------------------------------------------------
 struct MlpLayout {
@@ -1397,10 +1562,7 @@ struct Runner {
   int64_t E, N;
   hipStream_t stream;
   StageProfile* prof = nullptr;
-  bool want_forces = false;    // (set by run_model before forward())
-  bool ro_grad_done = false;   // forward(): readout_reduce also wrote d E / d (last readout hidden layer) -- no readout_backward launch
-  bool fwd_b3_done = false;    // forward_fused(): the readout-reverse chain ran in the tail of the fused forward (FusedForm::EightWaveTail, EightWaveDeepTail)
-  bool fwd_b2_done = false;    // ... and behind it the layer-1 moments reverse and the latent-0 reverse chain (FusedForm::EightWaveDeepTail)
+  StepPlan sp{};  // the launches of this step (choose_step): set by run_model, read everywhere below
 
   // per_edge / per_atom: operand elements the launch must move (each distinct operand row once); see DESIGN.md §5
   int mark(const char* name, double per_edge = 0, double per_atom = 0, double flops = 0) {
@@ -1664,9 +1826,6 @@ struct Runner {
     return m;
   }
 
-  // slot form of the single-layer pipeline (LinearPath::Slot); the debug taps name tensors it never forms
-  bool use_slot() const { return p->pipe.slot() && !p->taps; }
-
   TpOpArgs op_args(const aa_graph* g, int l) const {
     const aa_model_config& c = p->cfg;
     TpOpArgs o{};
@@ -1696,7 +1855,7 @@ struct Runner {
     }
     o.wk = wt(p->o_wk[l]);
     o.wt = wt(p->o_wt[l]);
-    if (use_slot()) {
+    if (sp.slot) {
       // env inputs are hidden pre-activations everywhere: scalar_embed_mlp's (env weights behind its output layer) for layer 0,
       // slot l of the dense-net buffer (= z_{l-1}) afterwards
       if (l == 0) {
@@ -1714,13 +1873,9 @@ struct Runner {
     o.ld_gscal = c.num_tensor;
     o.q = buf(w.q_op);
     o.num_layers = c.num_layers;
-    {
-      // split form (default): per-atom vectors through HBM, edge loops in lean kernels (tp_operator_fused: fused form)
-      const bool nosplit = p->opt.tp_operator_fused != 0;
-      o.bvec = (!nosplit && w.bvec_op) ? buf(w.bvec_op) : nullptr;
-      o.gmbuf = (!nosplit && w.bvec_op && w.gm_op) ? buf(w.gm_op) : nullptr;
-      o.mbuf = (!nosplit && w.mom_op) ? buf(w.mom_op) : nullptr;
-    }
+    o.bvec = sp.op_split ? buf(w.bvec_op) : nullptr;
+    o.gmbuf = sp.op_split_reverse ? buf(w.gm_op) : nullptr;
+    o.mbuf = sp.op_split ? buf(w.mom_op) : nullptr;
     o.ld_gw0 = p->W;
     o.ld_gsh = p->D;
     o.ka_lds = std::max(c.num_scalar, c.latent_mlp_width);
@@ -1728,13 +1883,6 @@ struct Runner {
     return o;
   }
 
-  // env projections of the operator kernels as batched linear-layer launches (ModelPipeline::op_proj): where there are enough
-  // atoms to fill the chip with 128-row tiles
-  bool use_proj(const aa_graph* g) const {
-    if (!(p->pipe.op_proj && w.bvec_op && w.mom_op && !p->opt.tp_operator_fused)) return false;
-    if (p->opt.op_proj_gemm == 1) return true;
-    return atom_end(g) - atom_begin(g) >= 4096;
-  }
   // one problem per spherical-harmonic component j (rows: atoms), weight matrix number r(j)
   int proj_gemm(const TpOpArgs& o, const GemmMatSet& ms, const T* a_base, int64_t a_ld, int64_t a_bs, T* c_base, int64_t c_ld, int64_t c_bs) {
     GemmArgs gm{};
@@ -1766,11 +1914,11 @@ struct Runner {
     const int u = p->cfg.num_tensor;
     TpOpArgs o = op_args(g, l);
     o.scal = buf(w.scal[l]);
-    if (use_proj(g)) {
+    if (sp.proj_forward) {
       o.proj_gemm = 1;
       if (int rc = launch_tp_op<T>(p->pipe.tp_op, l, false, o, stream, 1)) return rc;
       if (int rc = mark("tp_op_moments", p->D + o.ka)) return rc;
-      const GemmMatSet& ms = (l == 0 && use_slot()) ? p->s_pr0f : p->s_pr[l];
+      const GemmMatSet& ms = (l == 0 && sp.slot) ? p->s_pr0f : p->s_pr[l];
       if (int rc = proj_gemm(o, ms, buf(w.mom_op), int64_t(p->D) * o.ka, o.ka, buf(w.x2s[l]), int64_t(p->D) * u, u)) return rc;
       if (int rc = launch_tp_op<T>(p->pipe.tp_op, l, false, o, stream, 2)) return rc;
       return mark("tp_op_fwd", p->W + u, double(l + 1) * p->D * u);
@@ -1794,12 +1942,12 @@ struct Runner {
     // (split form: every forward kernel of this step stored its B_l next to the others -- the vectors the layer-0 reverse needs)
     o.bvec_ready = (o.bvec && !p->opt.op_recompute_bvecs) ? 1 : 0;
     const double elems = p->D + W + u + 2 * o.ka + p->D + (l == 0 ? W + double(L - 1) * u + p->D : 0);
-    if (use_proj(g) && w.dx2s_op) {
+    if (sp.proj_reverse) {
       o.proj_gemm = 1;
       o.dx2s = buf(w.dx2s_op);
       if (int rc = launch_tp_op<T>(p->pipe.tp_op, l, true, o, stream, 1)) return rc;
       if (int rc = mark("tp_op_bwd", elems - 2 * o.ka - p->D, double(L) * p->D * u)) return rc;
-      const GemmMatSet& ms = (l == 0 && use_slot()) ? p->s_prt0f : p->s_prt[l];
+      const GemmMatSet& ms = (l == 0 && sp.slot) ? p->s_prt0f : p->s_prt[l];
       if (int rc = proj_gemm(o, ms, buf(w.dx2s_op), int64_t(p->D) * u, u, buf(w.gm_op), int64_t(p->D) * o.ka, o.ka)) return rc;
       if (int rc = launch_tp_op<T>(p->pipe.tp_op, l, true, o, stream, 2)) return rc;
       return mark("tp_op_edge_env", 2 * o.ka + p->D);
@@ -1817,75 +1965,11 @@ struct Runner {
     return o;
   }
 
-  // the whole forward in one launch (aa_fused.hip): every center atom's edge segment fits one 32-row MFMA tile
-  bool use_fused_fwd(const aa_graph* g) const {
-    if (!(sizeof(T) == 4 && p->pipe.fused_fwd && !p->taps && g->max_degree > 0 && g->max_degree <= kFusedMaxDegree)) return false;
-    // (three species + the team exchange area exceed the 160 KB of LDS: such graphs run the staged pipeline)
-    if (fused_fwd_lds_bytes(p->cfg.num_types, g->max_degree > 32) > size_t(160) * 1024) return false;
-    if (g->max_degree <= 32) return true;  // one full-ish tile per atom: faster than the staged forward at every size
-    // Team form (2 / 4 tiles per atom): a tile costs the same whether 32 or 12 of its rows carry an edge, so it pays where
-    // the step is latency-bound (few tiles: one launch instead of seven) or the tiles are nearly full.  Measured on Si boxes
-    // at r_max 6 / 7 (44 / 73 edges per atom, profiles/archive/r03_p_*): 216-512 atoms 17-27 % faster than the staged step, 1 728
-    // atoms -2 % / +8 %, 10 648 atoms +10 % / +18 % slower (69 % / 57 % of the tile rows in use).
-    // (num_edges IS the edge count of the active block: the atom-block hint promises that every center with edges lies in
-    // [atom_begin, atom_end) -- verified on the device by graph_hint_check_kernel -- so rowptr[atom_end] - rowptr[atom_begin],
-    // which the host does not hold, equals g->num_edges)
-    const int64_t n_active = g->atom_end > g->atom_begin ? g->atom_end - g->atom_begin : g->num_atoms;
-    const int64_t tiles = n_active * (g->max_degree <= 64 ? 2 : 4);  // (upper bound: every atom at the class of the longest segment)
-    if (p->opt.fused_forward == 2 || p->opt.fused_forward == 4) return true;  // (A/B: the team / mixed form whenever segments fit it)
-    // Round 5: a box whose AVERAGE atom fills most of one tile but whose longest segment is a little over 32 (thermal disorder: a
-    // handful of Si atoms with 33..37 neighbours after 50 fs at 300 K) takes the MIXED form -- one-tile kernel over all atoms, the
-    // team kernel over the long ones only (launch_fused_fwd) -- instead of giving up the fused forward for the whole box
-    // (tools/md_loop.py at C4: staged 11.3 ms, team form for every atom 12.2 ms per step; profiles/r05_v2*_md_loop_*).
-    const double fill = double(g->num_edges) / (32.0 * double(std::max<int64_t>(n_active, 1)));
-    if (fill >= 0.6 && fill <= 1.15) return true;
-    return tiles <= kFusedTeamTilesSmall || double(g->num_edges) >= 0.85 * 32.0 * double(tiles);
-  }
-  // the staged forward chains in the same folded form as the fused forward (fold_embed_output, fold_latent_outputs): the hidden activations a_e /
-  // a_0 are stored where the embedding / lat_0 used to be (ChainLayer::kept_out), consumers run on the folded matrices.  What
-  // graphs with long segments -- dense systems, too large for the team form -- run.
-  bool fold_staged() const {
-    return p->pipe.chains() && p->pipe.tp_op < 0 && p->pipe.fold_embed_output && p->pipe.fold_latent_outputs && p->cfg.num_layers == 2 && !p->taps &&
-           !p->opt.staged_no_fold;
-  }
-  // did the forward of this step leave a_e in the embedding's slot (folded first stage / env weights in the reverse)?
-  bool folded_fwd(const aa_graph* g) const { return use_fused_fwd(g) || fold_staged(); }
-  // Form of the one-tile pass of the fused forward (FusedForm), decided here only.  The two-waves-per-SIMD forms (aa_fused8.hip)
-  // need a plan with fused_wide, the w0 rows, and a one-tile pass (no class lists, or the mixed form).  aa_plan_options.fused_narrow:
-  //  0: boxes that leave a CU at most one workgroup (n <= 4 per CU) run one wave per SIMD whatever the kernel: there the
-  //     register-rich one-wave form -- w0 held, operands kept split -- is the faster one (64 atoms 44 vs 48 us, profiles/r06_v4_ab_c2_*).
-  //     From kFusedTailAtomsPerCu atoms per CU on, eight waves with the readout-reverse chain of the reverse pass in the tail, where
-  //     that applies (forces requested, no team pass -- its atoms would miss it -- and the chain's folded weights): there the eight-wave
-  //     form is as fast as two four-wave workgroups and the chain's 0.75 ms of streaming disappear (C4 -0.45 ms same box,
-  //     profiles/r06_v19_*).  Otherwise two four-wave workgroups per CU.
-  //     Where the resident latent-0 chain would run behind it (fold_lat0_reverse, fp32, S = u = latent width = 64) the tail is the DEEP
-  //     one: the layer-1 moments reverse and that chain run in it too, and Runner::backward skips both launches (fwd_b2_done).
-  //  2: eight waves at any size, with the (deep) tail where it applies;  3: four waves at any size, no tail;  1: never (fused_wide is off);
-  //  4: eight waves at any size with the chain-only tail where a tail applies (A/B of the deep tail).
-  int fused_form(const FusedFwdArgs& a, FusedForm* form) const {
-    *form = FusedForm::OneWave;
-    const bool teams = a.tile_atoms != nullptr;
-    if (!p->pipe.fused_wide || !a.w0 || (teams && !a.mixed)) return AA_OK;
-    const int cus = device_cu_count();
-    if (cus < 0) return cus;
-    const int64_t n = a.atom_end - a.atom0;
-    const bool tail_ok = want_forces && !teams && p->pipe.chains() && p->pipe.fold_latent_outputs && p->cfg.num_layers == 2;
-    const bool deep_ok = tail_ok && p->pipe.fold_lat0_reverse && p->pipe.env_moments() && sizeof(T) == 4 && p->cfg.num_scalar == 64 &&
-                         p->cfg.num_tensor == 64 && p->cfg.latent_mlp_width == 64 && p->opt.fused_narrow != 4;
-    const FusedForm tail_form = deep_ok ? FusedForm::EightWaveDeepTail : FusedForm::EightWaveTail;
-    if (p->opt.fused_narrow == 2 || p->opt.fused_narrow == 4) {
-      *form = tail_ok ? tail_form : FusedForm::EightWave;
-    } else if (p->opt.fused_narrow == 3) {
-      *form = FusedForm::FourWave;
-    } else if (n > int64_t(4) * cus) {
-      *form = tail_ok && n >= int64_t(kFusedTailAtomsPerCu) * cus ? tail_form : FusedForm::FourWave;
-    }
-    return AA_OK;
-  }
+  // ---- the whole forward in one launch (aa_fused.hip; StepPlan::forward says when) -------------------------------------
 
-  int forward_fused(const aa_graph* g, const void* pos, void* atom_energy) {
+  // everything but the weight program
+  FusedFwdArgs fused_args(const aa_graph* g, const void* pos, void* atom_energy) const {
     const aa_model_config& c = p->cfg;
-    const int S = c.num_scalar, u = c.num_tensor;
     FusedFwdArgs a{};
     a.N = N;
     a.atom0 = atom_begin(g);
@@ -1899,52 +1983,19 @@ struct Runner {
     a.tile_atoms = nullptr;
     a.tile_counts = nullptr;
     a.tile_cap = 0;
-    if (g->max_degree > 32) {
+    if (sp.forward != ForwardKind::FusedOneTile) {
       a.tile_counts = reinterpret_cast<int32_t*>(buf(w.tiles));
       a.tile_atoms = a.tile_counts + 8;
       a.tile_cap = g->num_atoms;
-      // mixed form (one-tile pass over all atoms + team pass over the long ones) where long atoms are the minority -- boxes whose
-      // average atom fits one tile; dense boxes that took the team path because they are small or their tiles are full run the pure
-      // team form: there the one-tile launch would only skip.  2 / 4: the team / mixed form for every graph (A/B)
-      const int64_t n_act = g->atom_end > g->atom_begin ? g->atom_end - g->atom_begin : g->num_atoms;
-      const double fill = double(g->num_edges) / (32.0 * double(std::max<int64_t>(n_act, 1)));
-      a.mixed = p->opt.fused_forward == 2 ? 0 : (p->opt.fused_forward == 4 || fill <= 1.15) ? 1 : 0;
+      a.mixed = sp.forward == ForwardKind::FusedMixed ? 1 : 0;
     }
     a.num_types = c.num_types;
     a.embed_kind = c.embed_kind;
     a.spline_span = c.spline_span;
     a.poly_p = float(c.poly_p);
-    auto wf = [&](size_t off) { return reinterpret_cast<const float*>(wt(off)); };
-    auto bf = [&](size_t off) { return reinterpret_cast<float*>(buf(off)); };
     a.rmax_recip = wf(p->o_rmax);
     a.bessel_w = wf(p->o_bessel);
     a.emb_tab = wf(p->o_embtab_h);  // (folded: the table yields the first layer's pre-activation)
-    // the weight program of the kernel (see fused_fwd_kernel): 12-KB blocks in execution order.  The plan takes the fused forward
-    // only with every fold of its program packed (choose_pipeline: fold_embed_table, fold_embed_output, fold_latent_outputs)
-    int ns = 0;
-    FusedFwdArgs* prog = &a;  // (the program under construction: `a`, later the two-waves-per-SIMD form's copy)
-    auto add_layer = [&](const float* Wq, int KC, int tile0, int ntiles) {
-      for (int t = tile0; t < tile0 + ntiles; t += 2)
-        for (int kc = 0; kc < KC; ++kc) {
-          prog->wstep[ns][0] = Wq + (size_t(t) * KC + kc) * 64 * 24;
-          prog->wstep[ns][1] = Wq + (size_t(t + 1) * KC + kc) * 64 * 24;
-          ++ns;
-        }
-    };
-    auto add_env = [&](const float* Wk) {  // one env projection: 4 blocks of env-weight rows
-      for (int cblk = 0; cblk < 4; ++cblk) {
-        prog->wstep[ns][0] = Wk + size_t(cblk) * 16 * p->R * 64;
-        prog->wstep[ns][1] = Wk + size_t(cblk) * 16 * p->R * 64 + 1536;  // (blocks are loaded as 2 x 6 KB; 16 R 256 B are used)
-        ++ns;
-      }
-    };
-    add_env(wf(p->o_wk0f));
-    add_layer(wf(p->o_g0fq), 2, 0, 2 + 2 * p->R);
-    add_layer(wf(p->latent[0].wq[0]), 4, 0, 2);
-    add_env(wf(p->o_wk[1]));
-    add_layer(wf(p->o_lat1in_fq), 6, 0, 2);
-    add_layer(wf(p->o_ro0_fq), 6, 0, 2);
-    if (ns != fused_fwd_num_steps(p->R) || ns > kFusedMaxSteps) return fail(AA_ERR_INVALID, "fused forward: program length mismatch");
     a.tpw0 = wf(p->o_tpw[0]);
     a.tpw1 = wf(p->o_tpw[1]);
     a.coupling = c.tps[0].coupling;
@@ -1966,255 +2017,315 @@ struct Runner {
     a.x2s1 = bf(w.x2s[1]);
     a.atom_energy = static_cast<float*>(atom_energy);
     a.status = p->status;
-    FusedForm form;
-    if (int rc = fused_form(a, &form)) return rc;
-    // the two-waves-per-SIMD forms of the one-tile pass (aa_fused8.hip): their own step order -- Wenv0 | first stage | latent 0 |
-    // Wenv1 | latent 1: scal1 chunks | [lat0, two-body] chunks x {latent 1, readout} | readout: lat1 chunks [| readout-reverse chain]
-    FusedFwdArgs a8{};
-    if (form != FusedForm::OneWave) {
-      a8 = a;
-      ns = 0;
-      prog = &a8;
-      auto add_step = [&](const float* Wq, int KC, int kc) {  // one step: the tile pair (0, 1) x chunk kc of a KC-chunk layer
-        prog->wstep[ns][0] = Wq + (size_t(0) * KC + kc) * 64 * 24;
-        prog->wstep[ns][1] = Wq + (size_t(1) * KC + kc) * 64 * 24;
-        ++ns;
-      };
-      add_env(wf(p->o_wk0f));
-      add_layer(wf(p->o_g0fq), 2, 0, 2 + 2 * p->R);
-      add_layer(wf(p->latent[0].wq[0]), 4, 0, 2);
-      add_env(wf(p->o_wk[1]));
-      add_step(wf(p->o_lat1in_fq), 6, 4);
-      add_step(wf(p->o_lat1in_fq), 6, 5);
-      for (int kc : {2, 3, 0, 1}) {
-        add_step(wf(p->o_lat1in_fq), 6, kc);
-        add_step(wf(p->o_ro0_fq), 6, kc);
-      }
-      add_step(wf(p->o_ro0_fq), 6, 4);
-      add_step(wf(p->o_ro0_fq), 6, 5);
-      const bool deep = form == FusedForm::EightWaveDeepTail;
-      const bool tail = deep || form == FusedForm::EightWaveTail;
-      if (tail) {
-        add_layer(wf(p->o_b3af_q), 2, 0, 2);
-        add_layer(wf(p->pipe.fold_lat0_reverse ? p->o_b3bf_q : p->o_b3b_q), 4, 0, 4);
-        add_layer(wf(p->o_b3c_q), 2, 0, 2);
-        a8.g_fcat = bf(w.g_fcat);
-        a8.ld_gfcat = p->SL1;
-        a8.g_scal1 = bf(w.g_scal[1]);
-      }
-      if (deep) {  // + the transposed layer-1 env weights [R][u][64] as they are packed for tp_mom_bwd_last -- four windows of 48 of their
-                   //   64 R rows, the last one(s) pulled back inside the matrix (fused_fwd8_kernel: project_moments_t) -- and the first
-                   //   layer of latent 0, transposed (the resident chain's bytes)
-        for (int cblk = 0; cblk < 4; ++cblk) {
-          const int row0 = std::min(48 * cblk, 64 * p->R - 48);
-          prog->wstep[ns][0] = wf(p->o_wt[1]) + size_t(row0) * 64;
-          prog->wstep[ns][1] = wf(p->o_wt[1]) + size_t(row0) * 64 + 1536;
-          ++ns;
-        }
-        add_layer(wf(p->latent[0].wtq[0]), 2, 0, 4);
-        a8.g_scal0 = bf(w.g_scal[0]);
-        a8.gsh_env1 = bf(w.g_sh) + size_t(2) * size_t(E) * p->D;
-      }
-      if (ns != fused_fwd8_num_steps(p->R, deep ? 2 : tail ? 1 : 0)) return fail(AA_ERR_INVALID, "fused forward (wide): program length mismatch");
+    return a;
+  }
+  const float* wf(size_t off) const { return reinterpret_cast<const float*>(wt(off)); }
+  float* bf(size_t off) const { return reinterpret_cast<float*>(buf(off)); }
+
+  // the weight program of a fused-forward kernel under construction (see fused_fwd_kernel): 12-KB blocks in execution order
+  struct FusedProgram {
+    FusedFwdArgs& a;
+    int R;
+    int ns = 0;
+    void layer(const float* Wq, int KC, int tile0, int ntiles) {
+      for (int t = tile0; t < tile0 + ntiles; t += 2)
+        for (int kc = 0; kc < KC; ++kc) step(Wq + (size_t(t) * KC + kc) * 64 * 24, Wq + (size_t(t + 1) * KC + kc) * 64 * 24);
     }
-    if (int rc = mark("begin")) return rc;
-    if (int rc = launch_fused_fwd(p->pipe.chain_pair, form, a, form != FusedForm::OneWave ? &a8 : nullptr, stream)) return rc;
-    fwd_b2_done = form == FusedForm::EightWaveDeepTail && a.atom_end > a.atom0;  // (an empty block launches nothing)
-    fwd_b3_done = (fwd_b2_done || form == FusedForm::EightWaveTail) && a.atom_end > a.atom0;
-    // algorithmic traffic: neighbor id + shift in; unit vector, harmonics, five 64-wide rows and w0 out per edge;
-    // position, two x2s blocks, energy, row pointer per atom.  Flops: the linear layers of the forward (w0 counted once).
-    const double per_edge = 1 + (g->shift_vec ? 3 : 0) + 3 + 4 + p->D + 5 * 64 + p->W;
+    void chunk(const float* Wq, int KC, int kc) { step(Wq + size_t(kc) * 64 * 24, Wq + (size_t(KC) + kc) * 64 * 24); }  // the tile pair (0, 1) x chunk kc of a KC-chunk layer
+    void env(const float* Wk) {  // one env projection: 4 blocks of env-weight rows
+      for (int cblk = 0; cblk < 4; ++cblk) rows(Wk + size_t(cblk) * 16 * R * 64);
+    }
+    void rows(const float* W) { step(W, W + 1536); }  // (blocks are loaded as 2 x 6 KB; 16 R 256 B are used)
+    void step(const float* lo, const float* hi) {
+      if (ns < kFusedMaxSteps) {
+        a.wstep[ns][0] = lo;
+        a.wstep[ns][1] = hi;
+      }
+      ++ns;
+    }
+  };
+
+  // the one-wave form's program.  The plan takes the fused forward only with every fold of its program packed (choose_pipeline:
+  // fold_embed_table, fold_embed_output, fold_latent_outputs)
+  int fused_program_one_wave(FusedFwdArgs& a) const {
+    FusedProgram prog{a, p->R};
+    prog.env(wf(p->o_wk0f));
+    prog.layer(wf(p->o_g0fq), 2, 0, 2 + 2 * p->R);
+    prog.layer(wf(p->latent[0].wq[0]), 4, 0, 2);
+    prog.env(wf(p->o_wk[1]));
+    prog.layer(wf(p->o_lat1in_fq), 6, 0, 2);
+    prog.layer(wf(p->o_ro0_fq), 6, 0, 2);
+    if (prog.ns != fused_fwd_num_steps(p->R) || prog.ns > kFusedMaxSteps) return fail(AA_ERR_INVALID, "fused forward: program length mismatch");
+    return AA_OK;
+  }
+
+  // the program of the two-waves-per-SIMD forms of the one-tile pass (aa_fused8.hip): their own step order -- Wenv0 | first stage |
+  // latent 0 | Wenv1 | latent 1: scal1 chunks | [lat0, two-body] chunks x {latent 1, readout} | readout: lat1 chunks [| readout-reverse
+  // chain [| deep tail]] -- and what the tail writes
+  int fused_program_wide(FusedFwdArgs& a8, ReverseInForward tail) const {
+    FusedProgram prog{a8, p->R};
+    prog.env(wf(p->o_wk0f));
+    prog.layer(wf(p->o_g0fq), 2, 0, 2 + 2 * p->R);
+    prog.layer(wf(p->latent[0].wq[0]), 4, 0, 2);
+    prog.env(wf(p->o_wk[1]));
+    prog.chunk(wf(p->o_lat1in_fq), 6, 4);
+    prog.chunk(wf(p->o_lat1in_fq), 6, 5);
+    for (int kc : {2, 3, 0, 1}) {
+      prog.chunk(wf(p->o_lat1in_fq), 6, kc);
+      prog.chunk(wf(p->o_ro0_fq), 6, kc);
+    }
+    prog.chunk(wf(p->o_ro0_fq), 6, 4);
+    prog.chunk(wf(p->o_ro0_fq), 6, 5);
+    if (tail != ReverseInForward::None) {
+      prog.layer(wf(p->o_b3af_q), 2, 0, 2);
+      prog.layer(wf(p->pipe.fold_lat0_reverse ? p->o_b3bf_q : p->o_b3b_q), 4, 0, 4);
+      prog.layer(wf(p->o_b3c_q), 2, 0, 2);
+      a8.g_fcat = bf(w.g_fcat);
+      a8.ld_gfcat = p->SL1;
+      a8.g_scal1 = bf(w.g_scal[1]);
+    }
+    if (tail == ReverseInForward::ChainMomentsLatent0) {
+      // + the transposed layer-1 env weights [R][u][64] as they are packed for tp_mom_bwd_last -- four windows of 48 of their
+      //   64 R rows, the last one(s) pulled back inside the matrix (fused_fwd8_kernel: project_moments_t) -- and the first
+      //   layer of latent 0, transposed (the resident chain's bytes)
+      for (int cblk = 0; cblk < 4; ++cblk) prog.rows(wf(p->o_wt[1]) + size_t(std::min(48 * cblk, 64 * p->R - 48)) * 64);
+      prog.layer(wf(p->latent[0].wtq[0]), 2, 0, 4);
+      a8.g_scal0 = bf(w.g_scal[0]);
+      a8.gsh_env1 = bf(w.g_sh) + size_t(2) * size_t(E) * p->D;
+    }
+    if (prog.ns != fused_fwd8_num_steps(p->R, int(tail)) || prog.ns > kFusedMaxSteps) return fail(AA_ERR_INVALID, "fused forward (wide): program length mismatch");
+    return AA_OK;
+  }
+
+  // algorithmic traffic: neighbor id + shift in; unit vector, harmonics, five 64-wide rows and w0 out per edge;
+  // position, two x2s blocks, energy, row pointer per atom.  Flops: the linear layers of the forward (w0 counted once).
+  int mark_fused_fwd(const aa_graph* g) {
+    const int S = p->cfg.num_scalar, u = p->cfg.num_tensor;
+    double per_edge = 1 + (g->shift_vec ? 3 : 0) + 3 + 4 + p->D + 5 * 64 + p->W;
     const double per_atom = 3 + 2.0 * p->D * u + 1 + 1;
     double fl = 2.0 * double(E) * (2.0 * 64 * 64 + 64.0 * p->ng0 + double(S + u) * 64 + 64.0 * S + double(2 * S + u) * 64 + 64.0 * S + 3.0 * S * 64);
-    if (fwd_b3_done) {  // (+ the readout-reverse chain: 192 gradient columns out instead of two 64-wide pre-activation rows)
+    if (sp.reverse_in_forward != ReverseInForward::None) {  // (+ the readout-reverse chain: 192 gradient columns out instead of two 64-wide pre-activation rows)
       fl += 2.0 * double(E) * (64.0 * 64 + 128.0 * 128 + 64.0 * 64);
-      if (fwd_b2_done) {  // (+ the latent-0 reverse layer; out: d EDGE_FEATURES[:, :64], d scal0, d scal1, d Y instead of 192 columns; lat_h0 read again)
-        fl += 2.0 * double(E) * 64.0 * 128;
-        return mark("fused_fwd", per_edge + 64 + 64 + p->D, per_atom, fl);
-      }
-      return mark("fused_fwd", per_edge + 64, per_atom, fl);
+      per_edge += 64;
+    }
+    if (sp.reverse_in_forward == ReverseInForward::ChainMomentsLatent0) {  // (+ the latent-0 reverse layer; out: d EDGE_FEATURES[:, :64], d scal0, d scal1, d Y instead of 192 columns; lat_h0 read again)
+      fl += 2.0 * double(E) * 64.0 * 128;
+      per_edge += 64 + p->D;
     }
     return mark("fused_fwd", per_edge, per_atom, fl);
   }
 
-  int forward(const aa_graph* g, const void* pos, void* atom_energy) {
+  int forward_fused(const aa_graph* g, const void* pos, void* atom_energy) {
+    FusedFwdArgs a = fused_args(g, pos, atom_energy);
+    if (int rc = fused_program_one_wave(a)) return rc;  // (the team pass of the mixed form runs it whatever the one-tile pass's form)
+    if (sp.fused_form == FusedForm::OneWave) {
+      if (int rc = mark("begin")) return rc;
+      if (int rc = launch_fused_fwd(p->pipe.chain_pair, sp.fused_form, a, nullptr, stream)) return rc;
+      return mark_fused_fwd(g);
+    }
+    FusedFwdArgs a8 = a;
+    if (int rc = fused_program_wide(a8, fused_tail(sp.fused_form))) return rc;
+    if (int rc = mark("begin")) return rc;
+    if (int rc = launch_fused_fwd(p->pipe.chain_pair, sp.fused_form, a, &a8, stream)) return rc;
+    return mark_fused_fwd(g);
+  }
+
+  // ---- staged forward, stage by stage ----------------------------------------------------------------------------------
+
+  // 1-2: geometry, SH, radial-chemical embedding; 3: scalar_embed_mlp; 4+5a: env_embed_linear and
+  // first_layer_env_embed_projection as ONE GEMM (tensorembed.py:89, _allegro.py:251)
+  int fwd_first_stage(const aa_graph* g, const void* pos) {
     const aa_model_config& c = p->cfg;
-    const int S = c.num_scalar, u = c.num_tensor, L = c.num_layers, W = p->W, SL1 = p->SL1;
-    if (use_fused_fwd(g)) return forward_fused(g, pos, atom_energy);
-    // 1-2: geometry, SH, radial-chemical embedding
+    const int S = c.num_scalar, W = p->W, SL1 = p->SL1;
     if (int rc = mark("begin")) return rc;
     const double idx2 = 8.0 / sizeof(T);  // center + nbr ids, in elements
     if (int rc = launch_edge_prologue<T>(geom(g, pos), stream)) return rc;
     if (int rc = mark("edge_prologue", idx2 + 6 + (g->shift_vec ? 3 : 0) + 4 + p->D + c.embed_dim)) return rc;
-    const SegList none{0, {}};
-    const bool slot = use_slot();
-    const bool fstaged = fold_staged();
+    SegList in{1, {seg(buf(w.emb0), c.embed_dim, c.embed_dim)}};
     if (p->pipe.chains()) {
       // 3 + 4 + 5a as ONE kernel: emb0 -> h_e -> emb -> [two_body | w0]; hidden layers stay in registers
+      const SegList none{0, {}};
       ChainArgs ca{};
-      ca.nlayers = 3;
-      SegList in{1, {seg(buf(w.emb0), c.embed_dim, c.embed_dim)}};
       SegList c0{1, {seg(buf(w.se_h[0]), 64, 64)}};
       SegList c1{1, {seg(buf(w.emb), S, S)}};
       SegList c2{2, {seg(buf(w.fcat), SL1, S), seg(buf(w.w0), W, W)}};
       ca.L[0] = chain_layer(E, in, 0, wt(p->embed.wq[0]), c.embed_dim, 64, c0, nullptr, nullptr, nullptr, 0, 0, 1);
-      ca.L[1] = chain_layer(E, none, 0, wt(p->embed.wq[1]), 64, S, c1, nullptr, nullptr, nullptr, 1, 0, 0);
-      ca.L[2] = chain_layer(E, none, 0, wt(p->o_g0q), 64, p->ng0, c2, nullptr, nullptr, nullptr, 1, -1, 0);
-      if (fstaged) {
+      if (sp.forward == ForwardKind::StagedFolded) {
         // folded: a_e = silu(h_e) is stored where the embedding used to be; [two_body | w0] = a_e @ (W1 G0)
         ca.nlayers = 2;
         ca.L[0].kept_out = buf(w.emb);
         ca.L[0].ld_kept = S;
         ca.L[1] = chain_layer(E, none, 0, wt(p->o_g0fq), 64, p->ng0, c2, nullptr, nullptr, nullptr, 1, -1, 0);
+      } else {
+        ca.nlayers = 3;
+        ca.L[1] = chain_layer(E, none, 0, wt(p->embed.wq[1]), 64, S, c1, nullptr, nullptr, nullptr, 1, 0, 0);
+        ca.L[2] = chain_layer(E, none, 0, wt(p->o_g0q), 64, p->ng0, c2, nullptr, nullptr, nullptr, 1, -1, 0);
       }
-      if (int rc = run_chain(ca, "F1")) return rc;
-    } else if (slot) {
+      return run_chain(ca, "F1");
+    }
+    if (sp.slot) {
       // 3: hidden layers of scalar_embed_mlp; 4 + 5a on the activated last hidden layer (output layer folded into G0)
       const int De = c.embed_mlp_depth, He = c.embed_mlp_width;
-      SegList in{1, {seg(buf(w.emb0), c.embed_dim, c.embed_dim)}};
       SegList hid{1, {seg(buf(w.se_h[De - 1]), He, He)}};
       if (int rc = mlp_fwd(p->embed, De, in, w.se_h, hid, 0)) return rc;
       SegList out{2, {seg(buf(w.fcat), SL1, S), seg(buf(w.w0), W, W)}};
       act_now = c.act_kind[0];
-      if (int rc = gemm(hid, 1, p->s_g0f, out)) return rc;
+      return gemm(hid, 1, p->s_g0f, out);
+    }
+    SegList emb{1, {seg(buf(w.emb), S, S)}};
+    if (int rc = mlp_fwd(p->embed, c.embed_mlp_depth + 1, in, w.se_h, emb, 0)) return rc;
+    SegList out{3, {seg(buf(w.fcat), SL1, S), seg(buf(w.w0), W, W), seg(buf(w.envw[0]), W, W)}};
+    if (p->pipe.env_moments()) out.count = 2;
+    act_now = AA_ACT_SILU;  // (a plain linear map: no activation involved)
+    return gemm(emb, 0, wt(p->o_g0), wt(p->o_g0p), wt(p->o_g0q), S, p->ng0, out, nullptr, nullptr);
+  }
+
+  // operands both directions of a tensor-product layer take, per-edge kernels with compile-time tables (TpPath::Spec, SpecChain) ...
+  template <typename A>
+  void spec_operands(A& a, const aa_graph* g, int l) const {
+    a.E = E;
+    a.N = N;
+    a.rowptr = g->rowptr;
+    a.u = p->cfg.num_tensor;
+    a.sh = buf(w.sh);
+    a.ld_sh = p->D;
+    if (l == 0) {
+      a.w_x1 = buf(w.w0);
+      a.ld_w1 = p->W;
     } else {
-    // 3: scalar_embed_mlp
-    {
-      SegList in{1, {seg(buf(w.emb0), c.embed_dim, c.embed_dim)}};
-      SegList out{1, {seg(buf(w.emb), S, S)}};
-      if (int rc = mlp_fwd(p->embed, c.embed_mlp_depth + 1, in, w.se_h, out, 0)) return rc;
+      a.x1_dense = buf(w.tf[l - 1]);
     }
-    // 4+5a: env_embed_linear and first_layer_env_embed_projection as ONE GEMM (tensorembed.py:89, _allegro.py:251)
-    {
-      SegList in{1, {seg(buf(w.emb), S, S)}};
-      SegList out{3, {seg(buf(w.fcat), SL1, S), seg(buf(w.w0), W, W), seg(buf(w.envw[0]), W, W)}};
-      if (p->pipe.env_moments()) out.count = 2;
-      act_now = AA_ACT_SILU;  // (a plain linear map: no activation involved)
-      if (int rc = gemm(in, 0, wt(p->o_g0), wt(p->o_g0p), wt(p->o_g0q), S, p->ng0, out, nullptr, nullptr)) return rc;
-    }
-    }
-    // 5: layers
-    const double sfac = 1.0 / std::sqrt(c.avg_num_neighbors);
-    for (int l = 0; l < L; ++l) {
-      if (p->pipe.tp_op >= 0) {
-        if (int rc = run_op_fwd(g, l)) return rc;
-      } else if (p->pipe.env_moments()) {
+    a.w_env = buf(w.envw[l]);
+    a.ld_we = p->W;
+    a.weights = wt(p->o_tpw[l]);
+    a.coupling = p->cfg.tps[l].coupling;
+    a.sf = 1.0 / std::sqrt(p->cfg.avg_num_neighbors);
+    a.x2s = buf(w.x2s[l]);
+  }
+  // ... and on LDS coupling tables (TpPath::General)
+  template <typename A>
+  void general_operands(A& a, const aa_graph* g, int l) const {
+    a.E = E;
+    a.N = N;
+    a.rowptr = g->rowptr;
+    if (l == 0)
+      a.x1 = implicit(w.w0);
+    else
+      a.x1.dense = buf(w.tf[l - 1]);
+    a.x2 = implicit(w.envw[l]);
+    a.weights = wt(p->o_tpw[l]);
+    a.scatter_factor = 1.0 / std::sqrt(p->cfg.avg_num_neighbors);
+    a.x2s = buf(w.x2s[l]);
+  }
+
+  // 5: tensor-product layer l
+  int fwd_tp_layer(const aa_graph* g, int l) {
+    const int u = p->cfg.num_tensor, L = p->cfg.num_layers, W = p->W;
+    switch (p->pipe.tp) {
+      case TpPath::Operator:
+        return run_op_fwd(g, l);
+      case TpPath::Moments: {
         TpMomArgs m = mom_args(g);
         if (l == 0) {
           m.c.scal1 = buf(w.scal[0]);  // the first-layer kernel writes its scalars through this field
-          if (fstaged) m.wk0 = wt(p->o_wk0f);  // (its env input is a_e: env weights behind the output layer of scalar_embed_mlp)
+          if (sp.forward == ForwardKind::StagedFolded) m.wk0 = wt(p->o_wk0f);  // (its env input is a_e: env weights behind the output layer of scalar_embed_mlp)
           if (int rc = launch_tp_mom_fwd_first<T>(p->pipe.chain_pair, m, stream)) return rc;
-          if (int rc = mark("tp_mom_fwd_first", p->D + m.ka0 + W + u, double(p->D) * u)) return rc;
-        } else {
-          if (int rc = launch_tp_mom_fwd_last<T>(p->pipe.chain_pair, m, stream)) return rc;
-          if (int rc = mark("tp_mom_fwd_last", p->D + m.ka1 + W + u, 2.0 * p->D * u)) return rc;
+          return mark("tp_mom_fwd_first", p->D + m.ka0 + W + u, double(p->D) * u);
         }
-      } else if (p->pipe.chain_pair >= 0 && l == 1) {
-        if (int rc = launch_tp_chain_fwd_last<T>(p->pipe.chain_pair, chain_args(g), stream)) return rc;
-        if (int rc = mark("tp_chain_fwd_last", 2 * W + p->D + u, 2.0 * p->D * u)) return rc;
-      } else if (p->pipe.channel_minor()) {
+        if (int rc = launch_tp_mom_fwd_last<T>(p->pipe.chain_pair, m, stream)) return rc;
+        return mark("tp_mom_fwd_last", p->D + m.ka1 + W + u, 2.0 * p->D * u);
+      }
+      case TpPath::SpecChain:
+        if (l == 1) {
+          if (int rc = launch_tp_chain_fwd_last<T>(p->pipe.chain_pair, chain_args(g), stream)) return rc;
+          return mark("tp_chain_fwd_last", 2 * W + p->D + u, 2.0 * p->D * u);
+        }
+        [[fallthrough]];  // (layer 0 of the pair: the per-edge kernel, its [E,u,D] output not stored)
+      case TpPath::Spec: {
         TpSpecFwdArgs a{};
-        a.E = E;
-        a.N = N;
-        a.rowptr = g->rowptr;
-        a.u = u;
-        a.sh = buf(w.sh);
-        a.ld_sh = p->D;
-        if (l == 0) {
-          a.w_x1 = buf(w.w0);
-          a.ld_w1 = W;
-        } else {
-          a.x1_dense = buf(w.tf[l - 1]);
-        }
-        a.w_env = buf(w.envw[l]);
-        a.ld_we = W;
-        a.weights = wt(p->o_tpw[l]);
-        a.coupling = c.tps[l].coupling;
-        a.sf = sfac;
-        a.x2s = buf(w.x2s[l]);
+        spec_operands(a, g, l);
         a.out = (l < L - 1 && p->pipe.chain_pair < 0) ? buf(w.tf[l]) : nullptr;
         a.scal = buf(w.scal[l]);
         a.ld_scal = u;
         if (int rc = launch_tp_spec_fwd<T>(p->pipe.spec_sig[l], a, stream)) return rc;
-        if (int rc = mark("tp_spec_fwd", 2 * W + p->D + u, 2.0 * p->D * u)) return rc;
-      } else {
-      TpLayerFwdArgs a{};
-      a.E = E;
-      a.N = N;
-      a.rowptr = g->rowptr;
-      if (l == 0)
-        a.x1 = implicit(w.w0);
-      else
-        a.x1.dense = buf(w.tf[l - 1]);
-      a.x2 = implicit(w.envw[l]);
-      a.weights = wt(p->o_tpw[l]);
-      a.scatter_factor = sfac;
-      a.x2s = buf(w.x2s[l]);
-      a.out = l < L - 1 ? buf(w.tf[l]) : nullptr;
-      a.scal = buf(w.scal[l]);
-      a.ld_scal = u;
-      if (int rc = launch_tp_layer_fwd<T>(p->layers[l], a, stream)) return rc;
-      if (int rc = mark("tp_layer_fwd", 2 * W + p->D + u * p->D + u, 2.0 * p->D * u)) return rc;
+        return mark("tp_spec_fwd", 2 * W + p->D + u, 2.0 * p->D * u);
       }
-      if (p->pipe.chains()) {
-        ChainArgs ca{};
-        SegList in{2, {seg(buf(w.fcat), SL1, S * (l + 1)), seg(buf(w.scal[l]), u, u)}};
-        SegList ch{1, {seg(buf(w.lat_h[l][0]), 64, 64)}};
-        SegList cl{1, {seg(buf(w.fcat) + S * (l + 1), SL1, S)}};
-        ca.L[0] = chain_layer(E, in, 0, wt(p->latent[l].wq[0]), S * (l + 1) + u, 64, ch, nullptr, nullptr, nullptr, 0, 0, 1);
-        if (fstaged && l < L - 1) {
-          // folded: no output layer; a_l = silu(z_l) goes where lat_l used to be
-          ca.nlayers = 1;
-          ca.L[0].kept_out = buf(w.fcat) + S * (l + 1);
-          ca.L[0].ld_kept = SL1;
-        } else if (fstaged) {
-          // folded: latent 1 and the readout on [two-body | a_0 | ...] with the output layers folded into their row blocks; a_1 stays in registers
-          ca.nlayers = 2;
-          SegList fin{1, {seg(buf(w.fcat), SL1, S * L)}};
-          SegList cr{1, {seg(buf(w.ro_h[0]), 64, 64)}};
-          ca.L[0] = chain_layer(E, in, 0, wt(p->o_lat1in_fq), S * (l + 1) + u, 64, ch, nullptr, nullptr, nullptr, 0, 0, 1);
-          ca.L[1] = chain_layer(E, fin, 0, wt(p->o_ro0_fq), S * L + 64, 64, cr, nullptr, nullptr, nullptr, 1, -1, 0);
-          ca.L[1].edge_sum_out = buf(w.e_edge);
-          ca.ro_w = wt(p->o_ro_last);
-        } else if (l < L - 1) {
-          ca.nlayers = 2;
-          ca.L[1] = chain_layer(E, none, 0, wt(p->latent[l].wq[1]), 64, S, cl, nullptr, nullptr, nullptr, 1, -1, 0);
-        } else {
-          // last latent + the readout's GEMM layer: lat_{L-1} stays in registers as the tail of the readout input
-          ca.nlayers = 3;
-          SegList fin{1, {seg(buf(w.fcat), SL1, S * L)}};
-          SegList cr{1, {seg(buf(w.ro_h[0]), 64, 64)}};
-          ca.L[1] = chain_layer(E, none, 0, wt(p->latent[l].wq[1]), 64, S, cl, nullptr, nullptr, nullptr, 1, 0, 0);
-          ca.L[2] = chain_layer(E, fin, 0, wt(p->readout.wq[0]), S * L + 64, 64, cr, nullptr, nullptr, nullptr, 1, -1, 0);
-          ca.L[2].edge_sum_out = buf(w.e_edge);  // last linear readout layer folded into the epilogue
-          ca.ro_w = wt(p->o_ro_last);
-        }
-        if (int rc = run_chain(ca, "F2")) return rc;
-        continue;
+      case TpPath::General: {
+        TpLayerFwdArgs a{};
+        general_operands(a, g, l);
+        a.out = l < L - 1 ? buf(w.tf[l]) : nullptr;
+        a.scal = buf(w.scal[l]);
+        a.ld_scal = u;
+        if (int rc = launch_tp_layer_fwd<T>(p->layers[l], a, stream)) return rc;
+        return mark("tp_layer_fwd", 2 * W + p->D + u * p->D + u, 2.0 * p->D * u);
       }
-      if (slot) {
-        // hidden pre-activation z_l straight into slot l + 1; the earlier slots are activated on load (their output layers are
-        // folded into this layer's row blocks)
-        SegList in{2, {seg(buf(w.fcat), SL1, S * (l + 1)), seg(buf(w.scal[l]), u, u)}};
-        SegList zl{1, {seg(buf(w.fcat) + S * (l + 1), SL1, S)}};
-        act_now = c.act_kind[1];
-        if (int rc = gemm(in, l > 0, p->s_in[l], zl, nullptr, nullptr, S, S * (l + 1))) return rc;
-        continue;
-      }
-      SegList in{2, {seg(buf(w.fcat), SL1, S * (l + 1)), seg(buf(w.scal[l]), u, u)}};
-      SegList out;
-      out.count = (l < L - 1 && !p->pipe.env_moments()) ? 2 : 1;
-      out.s[0] = seg(buf(w.fcat) + S * (l + 1), SL1, S);
-      if (l < L - 1 && !p->pipe.env_moments()) out.s[1] = seg(buf(w.envw[l + 1]), W, W);
-      if (int rc = mlp_fwd(p->latent[l], c.latent_mlp_depth + 1, in, w.lat_h[l], out, 1)) return rc;
     }
-    // 6: edge readout GEMM layers, 7-8: last linear + edge sum + per-type scale/shift
+    return fail(AA_ERR_INVALID, "step plan: unknown tensor-product path");
+  }
+
+  // latent MLP l; on the chains the last one carries the readout's GEMM layer
+  int fwd_latent(int l) {
+    const aa_model_config& c = p->cfg;
+    const int S = c.num_scalar, u = c.num_tensor, L = c.num_layers, W = p->W, SL1 = p->SL1;
+    SegList in{2, {seg(buf(w.fcat), SL1, S * (l + 1)), seg(buf(w.scal[l]), u, u)}};
+    if (p->pipe.chains()) {
+      const SegList none{0, {}};
+      const bool folded = sp.forward == ForwardKind::StagedFolded;
+      ChainArgs ca{};
+      SegList ch{1, {seg(buf(w.lat_h[l][0]), 64, 64)}};
+      SegList cl{1, {seg(buf(w.fcat) + S * (l + 1), SL1, S)}};
+      SegList fin{1, {seg(buf(w.fcat), SL1, S * L)}};
+      SegList cr{1, {seg(buf(w.ro_h[0]), 64, 64)}};
+      ca.L[0] = chain_layer(E, in, 0, wt(p->latent[l].wq[0]), S * (l + 1) + u, 64, ch, nullptr, nullptr, nullptr, 0, 0, 1);
+      if (folded && l < L - 1) {
+        // folded: no output layer; a_l = silu(z_l) goes where lat_l used to be
+        ca.nlayers = 1;
+        ca.L[0].kept_out = buf(w.fcat) + S * (l + 1);
+        ca.L[0].ld_kept = SL1;
+      } else if (folded) {
+        // folded: latent 1 and the readout on [two-body | a_0 | ...] with the output layers folded into their row blocks; a_1 stays in registers
+        ca.nlayers = 2;
+        ca.L[0] = chain_layer(E, in, 0, wt(p->o_lat1in_fq), S * (l + 1) + u, 64, ch, nullptr, nullptr, nullptr, 0, 0, 1);
+        ca.L[1] = chain_layer(E, fin, 0, wt(p->o_ro0_fq), S * L + 64, 64, cr, nullptr, nullptr, nullptr, 1, -1, 0);
+        ca.L[1].edge_sum_out = buf(w.e_edge);
+        ca.ro_w = wt(p->o_ro_last);
+      } else if (l < L - 1) {
+        ca.nlayers = 2;
+        ca.L[1] = chain_layer(E, none, 0, wt(p->latent[l].wq[1]), 64, S, cl, nullptr, nullptr, nullptr, 1, -1, 0);
+      } else {
+        // last latent + the readout's GEMM layer: lat_{L-1} stays in registers as the tail of the readout input
+        ca.nlayers = 3;
+        ca.L[1] = chain_layer(E, none, 0, wt(p->latent[l].wq[1]), 64, S, cl, nullptr, nullptr, nullptr, 1, 0, 0);
+        ca.L[2] = chain_layer(E, fin, 0, wt(p->readout.wq[0]), S * L + 64, 64, cr, nullptr, nullptr, nullptr, 1, -1, 0);
+        ca.L[2].edge_sum_out = buf(w.e_edge);  // last linear readout layer folded into the epilogue
+        ca.ro_w = wt(p->o_ro_last);
+      }
+      return run_chain(ca, "F2");
+    }
+    if (sp.slot) {
+      // hidden pre-activation z_l straight into slot l + 1; the earlier slots are activated on load (their output layers are
+      // folded into this layer's row blocks)
+      SegList zl{1, {seg(buf(w.fcat) + S * (l + 1), SL1, S)}};
+      act_now = c.act_kind[1];
+      return gemm(in, l > 0, p->s_in[l], zl, nullptr, nullptr, S, S * (l + 1));
+    }
+    SegList out;
+    out.count = (l < L - 1 && !p->pipe.env_moments()) ? 2 : 1;
+    out.s[0] = seg(buf(w.fcat) + S * (l + 1), SL1, S);
+    if (l < L - 1 && !p->pipe.env_moments()) out.s[1] = seg(buf(w.envw[l + 1]), W, W);
+    return mlp_fwd(p->latent[l], c.latent_mlp_depth + 1, in, w.lat_h[l], out, 1);
+  }
+
+  // 6: edge readout GEMM layers (the chains ran theirs behind the last latent), 7-8: last linear + edge sum + per-type scale/shift
+  int fwd_readout(const aa_graph* g, void* atom_energy) {
+    const aa_model_config& c = p->cfg;
+    const int S = c.num_scalar, SL1 = p->SL1;
     if (c.readout_mlp_depth > 0 && !p->pipe.chains()) {
       act_now = c.act_kind[2];
       SegList a{1, {seg(buf(w.fcat), SL1, SL1)}};
       for (int i = 0; i < c.readout_mlp_depth; ++i) {
         SegList cs{1, {seg(buf(w.ro_h[i]), c.readout_mlp_width, c.readout_mlp_width)}};
-        if (slot && i == 0) {
+        if (sp.slot && i == 0) {
           act_now = c.act_kind[1];  // (the activated columns are the latents' hidden layers)
           if (int rc = gemm(a, 1, p->s_ro0, cs, nullptr, nullptr, S, SL1)) return rc;
           act_now = c.act_kind[2];
@@ -2226,10 +2337,19 @@ struct Runner {
       }
     }
     ReadoutArgs ra = readout_args(g, atom_energy);
-    ro_grad_done = want_forces && !p->pipe.chains() && c.readout_mlp_depth > 0 && !p->opt.readout_two_pass;
-    if (ro_grad_done) ra.g_h = buf(w.g_ro_h[c.readout_mlp_depth - 1]);
+    if (sp.readout_grad_in_reduce) ra.g_h = buf(w.g_ro_h[c.readout_mlp_depth - 1]);
     if (int rc = launch_readout_reduce<T>(ra, stream)) return rc;
-    return mark("readout_reduce", (p->pipe.chains() ? 1 : (c.readout_mlp_depth > 0 ? c.readout_mlp_width : SL1)) * (ro_grad_done ? 2.0 : 1.0), 1);
+    return mark("readout_reduce", (p->pipe.chains() ? 1 : (c.readout_mlp_depth > 0 ? c.readout_mlp_width : SL1)) * (sp.readout_grad_in_reduce ? 2.0 : 1.0), 1);
+  }
+
+  int forward(const aa_graph* g, const void* pos, void* atom_energy) {
+    if (sp.fused()) return forward_fused(g, pos, atom_energy);
+    if (int rc = fwd_first_stage(g, pos)) return rc;
+    for (int l = 0; l < p->cfg.num_layers; ++l) {
+      if (int rc = fwd_tp_layer(g, l)) return rc;
+      if (int rc = fwd_latent(l)) return rc;
+    }
+    return fwd_readout(g, atom_energy);
   }
 
   // geometry reverse + force assembly (the end of every reverse pass)
@@ -2243,7 +2363,7 @@ struct Runner {
     eb.num_gsh = num_gsh;
     eb.forces = forces;
     if (p->pipe.embed_fused) eb.t_in = buf(w.trev);
-    const bool gather = g->t_rowptr && g->t_perm;
+    const bool gather = sp.gather;
     eb.dvec = buf(w.dvec);
     eb.gather = gather ? 1 : 0;
     if (int rc = launch_edge_backward<T>(eb, stream)) return rc;
@@ -2263,14 +2383,14 @@ struct Runner {
     const aa_model_config& c = p->cfg;
     const int S = c.num_scalar, u = c.num_tensor, L = c.num_layers, W = p->W, SL1 = p->SL1;
     const int De = c.embed_mlp_depth, He = c.embed_mlp_width, Dr = c.readout_mlp_depth, Hr = c.readout_mlp_width, H = c.latent_mlp_width;
-    if (!(g->t_rowptr && g->t_perm)) AA_CHECK_HIP(hipMemsetAsync(forces, 0, size_t(N) * 3 * sizeof(T), stream));
+    if (sp.zero_forces) AA_CHECK_HIP(hipMemsetAsync(forces, 0, size_t(N) * 3 * sizeof(T), stream));
     if (int rc = mark("memset", 0, 3)) return rc;
     // readout: d (last hidden) from the energy, then its hidden layers down to the first one
     {
       ReadoutArgs r = readout_args(g, nullptr);
       r.g_h = buf(w.g_ro_h[Dr - 1]);
       act_now = c.act_kind[2];
-      if (!ro_grad_done) {
+      if (!sp.readout_grad_in_reduce) {
         if (int rc = launch_readout_backward<T>(r, stream)) return rc;
         if (int rc = mark("readout_backward", 2.0 * Hr)) return rc;
       }
@@ -2315,24 +2435,27 @@ struct Runner {
     return edge_tail(g, pos, forces);
   }
 
-  int backward(const aa_graph* g, const void* pos, void* forces) {
-    if (use_slot()) return backward_slot(g, pos, forces);
-    const aa_model_config& c = p->cfg;
-    const int S = c.num_scalar, u = c.num_tensor, L = c.num_layers, W = p->W, SL1 = p->SL1;
-    // spec path with u <= 64 writes every g_sh slot with plain stores; otherwise slots are accumulated into
-    const bool gsh_stores = (p->pipe.channel_minor() && u <= 64) || p->pipe.tp_op >= 0;
+  // ---- reverse pass, stage by stage (top down) ----------------------------------------------------------------------
+
+  // zeroes what the reverse pass accumulates into (StepPlan::zero_gsh / zero_forces)
+  int bwd_begin(void* forces) {
     const int num_gsh = num_gsh_slots(p);
-    if (!gsh_stores) AA_CHECK_HIP(hipMemsetAsync(buf(w.g_sh), 0, size_t(E) * p->D * num_gsh * sizeof(T), stream));
-    if (!(g->t_rowptr && g->t_perm)) AA_CHECK_HIP(hipMemsetAsync(forces, 0, size_t(N) * 3 * sizeof(T), stream));
-    if (int rc = mark("memset", gsh_stores ? 0 : p->D * num_gsh, 3)) return rc;
-    const SegList none{0, {}};
-    if (p->pipe.chains() && fwd_b3_done) {
+    if (sp.zero_gsh) AA_CHECK_HIP(hipMemsetAsync(buf(w.g_sh), 0, size_t(E) * p->D * num_gsh * sizeof(T), stream));
+    if (sp.zero_forces) AA_CHECK_HIP(hipMemsetAsync(forces, 0, size_t(N) * 3 * sizeof(T), stream));
+    return mark("memset", sp.zero_gsh ? p->D * num_gsh : 0, 3);
+  }
+
+  // readout reverse; on the chains with the last latent's reverse in the same kernel
+  int bwd_readout(const aa_graph* g) {
+    const aa_model_config& c = p->cfg;
+    const int S = c.num_scalar, u = c.num_tensor, L = c.num_layers, SL1 = p->SL1;
+    if (p->pipe.chains()) {
       // (the fused forward of this step ran this chain in its tail: d EDGE_FEATURES[:, :S L] and d scal_{L-1} are in the workspace)
-    } else if (p->pipe.chains()) {
+      if (sp.reverse_in_forward != ReverseInForward::None) return AA_OK;
       // readout reverse + last latent reverse in ONE kernel; d_lat_{L-1} and d_h never leave registers
+      const SegList none{0, {}};
       ReadoutArgs r = readout_args(g, nullptr);
       ChainArgs ca{};
-      ca.nlayers = 3;
       ca.ro_w = r.w;
       ca.ro_factor = r.factor;
       ca.ro_scales = r.scales;
@@ -2347,13 +2470,6 @@ struct Runner {
       SegList z1{1, {seg(buf(w.lat_h[L - 1][0]), 64, 64)}};
       SegList c2{1, {seg(buf(w.g_fcat), SL1, S * L)}};
       SegList c3{1, {seg(buf(w.g_scal[L - 1]), u, u)}};
-      ca.nlayers = 4;
-      ca.L[0] = chain_layer(E, in, 0, wt(p->o_b3a_q), 64, S, cn, nullptr, nullptr, nullptr, 0, 0, 0);
-      ca.L[0].a_mode = 1;
-      ca.L[1] = chain_layer(E, none, 0, wt(p->latent[L - 1].wtq[1]), S, 64, cn, nullptr, &z1, nullptr, 1, 0, 0);
-      ca.L[2] = chain_layer(E, in, 0, wt(p->o_b3b_q), 128, S * L, c2, nullptr, nullptr, nullptr, 1, -1, 0);
-      ca.L[2].a_mode = 1;
-      ca.L[3] = chain_layer(E, none, 0, wt(p->o_b3c_q), 64, u, c3, nullptr, nullptr, nullptr, 1, -1, 0);
       if (p->pipe.fold_latent_outputs && L == 2) {
         // "d lat1 = d ro_h @ Wro[lat1]^T" and "d a1 = d lat1 @ Wout_1^T" as ONE 64x64 layer (folded at pack time): 12 instead of 14 steps
         ca.nlayers = 3;
@@ -2362,109 +2478,125 @@ struct Runner {
         ca.L[1] = chain_layer(E, in, 0, wt(p->pipe.fold_lat0_reverse ? p->o_b3bf_q : p->o_b3b_q), 128, S * L, c2, nullptr, nullptr, nullptr, 1, -1, 0);
         ca.L[1].a_mode = 1;
         ca.L[2] = chain_layer(E, none, 0, wt(p->o_b3c_q), 64, u, c3, nullptr, nullptr, nullptr, 1, -1, 0);
-      }
-      if (int rc = run_chain(ca, "B3")) return rc;
-    } else
-    // readout
-    {
-      ReadoutArgs r = readout_args(g, nullptr);
-      if (c.readout_mlp_depth > 0) {
-        r.g_h = buf(w.g_ro_h[c.readout_mlp_depth - 1]);
-        act_now = c.act_kind[2];
-        if (!ro_grad_done) {
-          if (int rc = launch_readout_backward<T>(r, stream)) return rc;
-          if (int rc = mark("readout_backward", 2.0 * (c.readout_mlp_depth > 0 ? c.readout_mlp_width : SL1))) return rc;
-        }
-        SegList a{1, {seg(r.g_h, c.readout_mlp_width, c.readout_mlp_width)}};
-        for (int i = c.readout_mlp_depth - 1; i >= 0; --i) {
-          SegList cs, z;
-          const SegList* zp = nullptr;
-          if (i > 0) {
-            cs = SegList{1, {seg(buf(w.g_ro_h[i - 1]), c.readout_mlp_width, c.readout_mlp_width)}};
-            z = SegList{1, {seg(buf(w.ro_h[i - 1]), c.readout_mlp_width, c.readout_mlp_width)}};
-            zp = &z;
-          } else {
-            cs = SegList{1, {seg(buf(w.g_fcat), SL1, SL1)}};
-          }
-          if (int rc = gemm(a, 0, wt(p->readout.wt[i]), wt(p->readout.wtp[i]), wt(p->readout.wtq[i]), p->readout.dims[i + 1], p->readout.dims[i], cs,
-                            nullptr, zp))
-            return rc;
-          a = cs;
-        }
       } else {
-        r.g_h = buf(w.g_fcat);
-        if (int rc = launch_readout_backward<T>(r, stream)) return rc;
-        if (int rc = mark("readout_backward", 2.0 * (c.readout_mlp_depth > 0 ? c.readout_mlp_width : SL1))) return rc;
+        ca.nlayers = 4;
+        ca.L[0] = chain_layer(E, in, 0, wt(p->o_b3a_q), 64, S, cn, nullptr, nullptr, nullptr, 0, 0, 0);
+        ca.L[0].a_mode = 1;
+        ca.L[1] = chain_layer(E, none, 0, wt(p->latent[L - 1].wtq[1]), S, 64, cn, nullptr, &z1, nullptr, 1, 0, 0);
+        ca.L[2] = chain_layer(E, in, 0, wt(p->o_b3b_q), 128, S * L, c2, nullptr, nullptr, nullptr, 1, -1, 0);
+        ca.L[2].a_mode = 1;
+        ca.L[3] = chain_layer(E, none, 0, wt(p->o_b3c_q), 64, u, c3, nullptr, nullptr, nullptr, 1, -1, 0);
       }
+      return run_chain(ca, "B3");
     }
-    const double sfac = 1.0 / std::sqrt(c.avg_num_neighbors);
-    for (int l = L - 1; l >= 0; --l) {
-      // latent MLP reverse
-      if (p->pipe.chains() && l == L - 1) {
-        // (already done inside the readout chain above)
-      } else if (p->pipe.chains()) {
-        ChainArgs ca{};
+    ReadoutArgs r = readout_args(g, nullptr);
+    if (c.readout_mlp_depth == 0) {
+      r.g_h = buf(w.g_fcat);
+      if (int rc = launch_readout_backward<T>(r, stream)) return rc;
+      return mark("readout_backward", 2.0 * SL1);
+    }
+    r.g_h = buf(w.g_ro_h[c.readout_mlp_depth - 1]);
+    act_now = c.act_kind[2];
+    if (!sp.readout_grad_in_reduce) {
+      if (int rc = launch_readout_backward<T>(r, stream)) return rc;
+      if (int rc = mark("readout_backward", 2.0 * c.readout_mlp_width)) return rc;
+    }
+    SegList a{1, {seg(r.g_h, c.readout_mlp_width, c.readout_mlp_width)}};
+    for (int i = c.readout_mlp_depth - 1; i >= 0; --i) {
+      SegList cs, z;
+      const SegList* zp = nullptr;
+      if (i > 0) {
+        cs = SegList{1, {seg(buf(w.g_ro_h[i - 1]), c.readout_mlp_width, c.readout_mlp_width)}};
+        z = SegList{1, {seg(buf(w.ro_h[i - 1]), c.readout_mlp_width, c.readout_mlp_width)}};
+        zp = &z;
+      } else {
+        cs = SegList{1, {seg(buf(w.g_fcat), SL1, SL1)}};
+      }
+      if (int rc = gemm(a, 0, wt(p->readout.wt[i]), wt(p->readout.wtp[i]), wt(p->readout.wtq[i]), p->readout.dims[i + 1], p->readout.dims[i], cs,
+                        nullptr, zp))
+        return rc;
+      a = cs;
+    }
+    return AA_OK;
+  }
+
+  // reverse of latent MLP l
+  int bwd_latent(int l) {
+    const aa_model_config& c = p->cfg;
+    const int S = c.num_scalar, u = c.num_tensor, L = c.num_layers, W = p->W, SL1 = p->SL1;
+    if (p->pipe.chains() && l == L - 1) return AA_OK;  // (already done inside the readout chain)
+    const SegList none{0, {}};
+    ChainArgs ca{};
+    SegList in{1, {seg(buf(w.g_fcat) + S * (l + 1), SL1, S)}};
+    SegList c1{2, {seg(buf(w.g_fcat), SL1, S * (l + 1)), seg(buf(w.g_scal[l]), u, u)}};
+    int acc1[3] = {1, 0, 0};
+    switch (sp.latent_reverse) {
+      case LatentReverse::Mlp: {
+        SegList go;
+        go.count = (l < L - 1 && !p->pipe.env_moments()) ? 2 : 1;
+        go.s[0] = seg(buf(w.g_fcat) + S * (l + 1), SL1, S);
+        if (l < L - 1 && !p->pipe.env_moments()) go.s[1] = seg(buf(w.g_envw), W, W);
+        SegList aenv{1, {seg(p->pipe.env_moments() ? buf(w.g_aenv) : nullptr, c.latent_mlp_width, c.latent_mlp_width)}};
+        const SegList* addp = (p->pipe.env_moments() && l < L - 1) ? &aenv : nullptr;
+        return mlp_bwd(p->latent[l], c.latent_mlp_depth + 1, go, w.lat_h[l], w.g_lat_h, c1, acc1, 1, addp);
+      }
+      case LatentReverse::InForwardTail:  // (ran in the deep tail of the fused forward)
+        return AA_OK;
+      case LatentReverse::TwoLayerChain: {
         ca.nlayers = 2;
-        SegList in{1, {seg(buf(w.g_fcat) + S * (l + 1), SL1, S)}};
         SegList cn{1, {seg(nullptr, 64, 64)}};
         SegList zz{1, {seg(buf(w.lat_h[l][0]), 64, 64)}};
         SegList ad{1, {seg(buf(w.g_aenv), 64, 64)}};
-        SegList c1{2, {seg(buf(w.g_fcat), SL1, S * (l + 1)), seg(buf(w.g_scal[l]), u, u)}};
-        int acc1[3] = {1, 0, 0};
         ca.L[0] = chain_layer(E, in, 0, wt(p->latent[l].wtq[1]), S, 64, cn, nullptr, &zz, &ad, 0, 0, 0);
         ca.L[1] = chain_layer(E, none, 0, wt(p->latent[l].wtq[0]), 64, S * (l + 1) + u, c1, acc1, nullptr, nullptr, 1, -1, 0);
-        if (fwd_b2_done && l == 0) goto b2_done;  // (ran in the deep tail of the fused forward)
-        if (p->pipe.fold_lat0_reverse && L == 2 && l == 0) {
-          // the readout-reverse chain already applied Wout_0^T (folded into its lat0 columns): what is left of the output layer's
-          // reverse is elementwise -- d h = (d a_0 + d a_0 of the moments) x silu'(h) -- and rides as the operand transform of the
-          // first-layer reverse: ONE layer, 4 steps instead of 6
-          ca.nlayers = 1;
-          ca.L[0] = chain_layer(E, in, 0, wt(p->latent[l].wtq[0]), 64, S * (l + 1) + u, c1, acc1, nullptr, nullptr, 0, -1, 0);
-          ca.L[0].a_mode = 2;
-          ca.L[0].a2_add = buf(w.g_aenv);
-          ca.L[0].ld_a2add = 64;
-          ca.L[0].a2_z = buf(w.lat_h[l][0]);
-          ca.L[0].ld_a2z = 64;
-          if (sizeof(T) == 4 && S == 64 && u == 64 && !p->opt.chain_staged_weights) {
-            // the same layer with its 48 KB of weights resident in LDS (aa_chain_res.hip): one persistent workgroup per CU, no
-            // per-workgroup staging, no barriers in the row loop
-            ChainB2Args b2{};
-            b2.M = E;
-            b2.a = reinterpret_cast<const float*>(buf(w.g_fcat)) + S * (l + 1);
-            b2.lda = SL1;
-            b2.add = reinterpret_cast<const float*>(buf(w.g_aenv));
-            b2.ldadd = 64;
-            b2.z = reinterpret_cast<const float*>(buf(w.lat_h[l][0]));
-            b2.ldz = 64;
-            b2.Wq = wt(p->latent[l].wtq[0]);
-            b2.c0 = reinterpret_cast<float*>(buf(w.g_fcat));
-            b2.ldc0 = SL1;
-            b2.c1 = reinterpret_cast<float*>(buf(w.g_scal[l]));
-            b2.ldc1 = u;
-            if (int rc = launch_chain_b2_resident(b2, stream)) return rc;
-            if (int rc = mark("gc_64x128", gemm_row_elems(ca.L[0].g, true) + 2.0 * 64, 0, 2.0 * double(E) * 64 * 128)) return rc;
-            goto b2_done;
-          }
+        return run_chain(ca, "B2");
+      }
+      case LatentReverse::FoldedChain:
+      case LatentReverse::Resident:
+        // the readout-reverse chain already applied Wout_0^T (folded into its lat0 columns): what is left of the output layer's
+        // reverse is elementwise -- d h = (d a_0 + d a_0 of the moments) x silu'(h) -- and rides as the operand transform of the
+        // first-layer reverse: ONE layer, 4 steps instead of 6
+        ca.nlayers = 1;
+        ca.L[0] = chain_layer(E, in, 0, wt(p->latent[l].wtq[0]), 64, S * (l + 1) + u, c1, acc1, nullptr, nullptr, 0, -1, 0);
+        ca.L[0].a_mode = 2;
+        ca.L[0].a2_add = buf(w.g_aenv);
+        ca.L[0].ld_a2add = 64;
+        ca.L[0].a2_z = buf(w.lat_h[l][0]);
+        ca.L[0].ld_a2z = 64;
+        if (sp.latent_reverse == LatentReverse::FoldedChain) return run_chain(ca, "B2");
+        {
+          // the same layer with its 48 KB of weights resident in LDS (aa_chain_res.hip): one persistent workgroup per CU, no
+          // per-workgroup staging, no barriers in the row loop
+          ChainB2Args b2{};
+          b2.M = E;
+          b2.a = reinterpret_cast<const float*>(buf(w.g_fcat)) + S * (l + 1);
+          b2.lda = SL1;
+          b2.add = reinterpret_cast<const float*>(buf(w.g_aenv));
+          b2.ldadd = 64;
+          b2.z = reinterpret_cast<const float*>(buf(w.lat_h[l][0]));
+          b2.ldz = 64;
+          b2.Wq = wt(p->latent[l].wtq[0]);
+          b2.c0 = reinterpret_cast<float*>(buf(w.g_fcat));
+          b2.ldc0 = SL1;
+          b2.c1 = reinterpret_cast<float*>(buf(w.g_scal[l]));
+          b2.ldc1 = u;
+          if (int rc = launch_chain_b2_resident(b2, stream)) return rc;
+          return mark("gc_64x128", gemm_row_elems(ca.L[0].g, true) + 2.0 * 64, 0, 2.0 * double(E) * 64 * 128);
         }
-        if (int rc = run_chain(ca, "B2")) return rc;
-      b2_done:;
-      } else {
-      SegList go;
-      go.count = (l < L - 1 && !p->pipe.env_moments()) ? 2 : 1;
-      go.s[0] = seg(buf(w.g_fcat) + S * (l + 1), SL1, S);
-      if (l < L - 1 && !p->pipe.env_moments()) go.s[1] = seg(buf(w.g_envw), W, W);
-      SegList aenv{1, {seg(p->pipe.env_moments() ? buf(w.g_aenv) : nullptr, c.latent_mlp_width, c.latent_mlp_width)}};
-      const SegList* addp = (p->pipe.env_moments() && l < L - 1) ? &aenv : nullptr;
-      SegList gi{2, {seg(buf(w.g_fcat), SL1, S * (l + 1)), seg(buf(w.g_scal[l]), u, u)}};
-      int acc[3] = {1, 0, 0};
-      if (int rc = mlp_bwd(p->latent[l], c.latent_mlp_depth + 1, go, w.lat_h[l], w.g_lat_h, gi, acc, 1, addp)) return rc;
-      }
-      // tensor-product layer reverse
-      if (p->pipe.tp_op >= 0) {
-        if (int rc = run_op_bwd(g, l)) return rc;
-        continue;
-      }
-      if (p->pipe.env_moments()) {
+    }
+    return fail(AA_ERR_INVALID, "step plan: unknown latent reverse form");
+  }
+
+  // reverse of tensor-product layer l
+  int bwd_tp_layer(const aa_graph* g, int l) {
+    const aa_model_config& c = p->cfg;
+    const int S = c.num_scalar, u = c.num_tensor, L = c.num_layers, W = p->W;
+    switch (p->pipe.tp) {
+      case TpPath::Operator:
+        return run_op_bwd(g, l);
+      case TpPath::Moments: {
+        // (ran in the deep tail of the fused forward: the layer-1 slab of d Y is in the workspace, d a_0 was consumed there)
+        if (l == 1 && sp.reverse_in_forward == ReverseInForward::ChainMomentsLatent0) return AA_OK;
         TpMomArgs m = mom_args(g);
         m.c.gscal0 = buf(w.g_scal[0]);
         m.c.gscal1 = buf(w.g_scal[1]);
@@ -2472,23 +2604,19 @@ struct Runner {
         m.c.gsh_x1 = buf(w.g_sh);
         m.c.gsh_env = buf(w.g_sh) + size_t(l + 1) * size_t(E) * p->D;
         m.g_a = buf(w.g_aenv);
-        if (l == 1 && fwd_b2_done) {
-          // (ran in the deep tail of the fused forward: the layer-1 slab of d Y is in the workspace, d a_0 was consumed there)
-        } else if (l == 1) {
+        if (l == 1) {
           m.ld_ga = c.latent_mlp_width;
           if (int rc = launch_tp_mom_bwd_last<T>(p->pipe.chain_pair, m, stream)) return rc;
-          if (int rc = mark("tp_mom_bwd_last", p->D + W + u + 2 * m.ka1 + p->D, double(p->D) * u)) return rc;
-        } else {
-          m.ld_ga = S;
-          // (after a fused forward the embedding's slot holds a_e = silu(h) of scalar_embed_mlp and the env weights are folded behind
-          //  its output layer, fold_embed_output: d a_e comes out instead of d emb)
-          if (p->pipe.fold_embed_output && folded_fwd(g)) m.wt0 = wt(p->o_wt0f);
-          if (int rc = launch_tp_mom_bwd_first<T>(p->pipe.chain_pair, m, stream)) return rc;
-          if (int rc = mark("tp_mom_bwd_first", p->D + 2 * W + 2 * u + 2 * m.ka0 + 2 * p->D, 2.0 * p->D * u)) return rc;
+          return mark("tp_mom_bwd_last", p->D + W + u + 2 * m.ka1 + p->D, double(p->D) * u);
         }
-        continue;
+        m.ld_ga = S;
+        // (after a fused forward the embedding's slot holds a_e = silu(h) of scalar_embed_mlp and the env weights are folded behind
+        //  its output layer, fold_embed_output: d a_e comes out instead of d emb)
+        if (sp.folded_first_stage()) m.wt0 = wt(p->o_wt0f);
+        if (int rc = launch_tp_mom_bwd_first<T>(p->pipe.chain_pair, m, stream)) return rc;
+        return mark("tp_mom_bwd_first", p->D + 2 * W + 2 * u + 2 * m.ka0 + 2 * p->D, 2.0 * p->D * u);
       }
-      if (p->pipe.chain_pair >= 0) {
+      case TpPath::SpecChain: {
         TpChainArgs a = chain_args(g);
         a.gscal0 = buf(w.g_scal[0]);
         a.gscal1 = buf(w.g_scal[1]);
@@ -2498,36 +2626,20 @@ struct Runner {
         a.gsh_env = buf(w.g_sh) + size_t(l + 1) * size_t(E) * p->D;
         if (l == 1) {
           if (int rc = launch_tp_chain_bwd_last<T>(p->pipe.chain_pair, a, stream)) return rc;
-          if (int rc = mark("tp_chain_bwd_last", 3 * W + 2 * p->D + u, 2.0 * p->D * u)) return rc;
-        } else {
-          if (int rc = launch_tp_chain_bwd_first<T>(p->pipe.chain_pair, a, stream)) return rc;
-          if (int rc = mark("tp_chain_bwd_first", 4 * W + 3 * p->D + 2 * u, 2.0 * p->D * u)) return rc;
+          return mark("tp_chain_bwd_last", 3 * W + 2 * p->D + u, 2.0 * p->D * u);
         }
-        continue;
+        if (int rc = launch_tp_chain_bwd_first<T>(p->pipe.chain_pair, a, stream)) return rc;
+        return mark("tp_chain_bwd_first", 4 * W + 3 * p->D + 2 * u, 2.0 * p->D * u);
       }
-      if (p->pipe.channel_minor()) {
+      case TpPath::Spec: {
         TpSpecBwdArgs a{};
-        a.E = E;
-        a.N = N;
-        a.rowptr = g->rowptr;
-        a.u = u;
-        a.sh = buf(w.sh);
-        a.ld_sh = p->D;
+        spec_operands(a, g, l);
         if (l == 0) {
-          a.w_x1 = buf(w.w0);
-          a.ld_w1 = W;
           a.g_w1 = buf(w.g_w0);
           a.ld_gw1 = W;
         } else {
-          a.x1_dense = buf(w.tf[l - 1]);
           a.g_x1_dense = buf(w.g_tf[(l - 1) & 1]);
         }
-        a.w_env = buf(w.envw[l]);
-        a.ld_we = W;
-        a.weights = wt(p->o_tpw[l]);
-        a.coupling = c.tps[l].coupling;
-        a.sf = sfac;
-        a.x2s = buf(w.x2s[l]);
         a.gout = l < L - 1 ? buf(w.g_tf[l & 1]) : nullptr;
         a.gscal = buf(w.g_scal[l]);
         a.ld_gscal = u;
@@ -2537,109 +2649,112 @@ struct Runner {
         a.gsh_env = buf(w.g_sh) + size_t(l + 1) * size_t(E) * p->D;
         a.ld_gsh = p->D;
         if (int rc = launch_tp_spec_bwd<T>(p->pipe.spec_sig[l], a, stream)) return rc;
-        if (int rc = mark("tp_spec_bwd", 4 * W + 3 * p->D + 2 * u * p->D + u, 2.0 * p->D * u)) return rc;
-        continue;
+        return mark("tp_spec_bwd", 4 * W + 3 * p->D + 2 * u * p->D + u, 2.0 * p->D * u);
       }
-      TpLayerBwdArgs a{};
-      a.E = E;
-      a.N = N;
-      a.rowptr = g->rowptr;
-      if (l == 0)
-        a.x1 = implicit(w.w0);
-      else
-        a.x1.dense = buf(w.tf[l - 1]);
-      a.x2 = implicit(w.envw[l]);
-      a.weights = wt(p->o_tpw[l]);
-      a.scatter_factor = sfac;
-      a.x2s = buf(w.x2s[l]);
-      a.gout = l < L - 1 ? buf(w.g_tf[l & 1]) : nullptr;
-      a.gscal = buf(w.g_scal[l]);
-      a.ld_gscal = u;
-      if (l == 0) {
-        a.g1.gw = buf(w.g_w0);
-        a.g1.ldgw = W;
-        a.g1.gsh = buf(w.g_sh);
-        a.g1.ld_gsh = p->D;
-      } else {
-        a.g1.dense = buf(w.g_tf[(l - 1) & 1]);
-      }
-      a.g2.gw = buf(w.g_envw);
-      a.g2.ldgw = W;
-      a.g2.gsh = buf(w.g_sh);
-      a.g2.ld_gsh = p->D;
-      if (int rc = launch_tp_layer_bwd<T>(p->layers[l], a, stream)) return rc;
-      if (int rc = mark("tp_layer_bwd", 4 * W + 2 * p->D + 2 * u * p->D + u, 2.0 * p->D * u)) return rc;
-    }
-    if (p->pipe.chains()) {
-      // first-stage reverse + scalar_embed_mlp reverse in ONE kernel
-      ChainArgs ca{};
-      ca.nlayers = 3;
-      SegList in{2, {seg(buf(w.g_fcat), SL1, S), seg(buf(w.g_w0), W, W)}};
-      SegList cn{1, {seg(nullptr, 64, 64)}};
-      SegList ad{1, {seg(buf(w.g_aenv), S, S)}};
-      SegList zz{1, {seg(buf(w.se_h[0]), 64, 64)}};
-      SegList ce{1, {seg(buf(w.g_emb0), c.embed_dim, c.embed_dim)}};
-      ca.L[0] = chain_layer(E, in, 0, wt(p->o_g0tq), p->ng0, S, cn, nullptr, nullptr, &ad, 0, 0, 0);
-      ca.L[1] = chain_layer(E, none, 0, wt(p->embed.wtq[1]), S, 64, cn, nullptr, &zz, nullptr, 1, 0, 0);
-      ca.L[2] = chain_layer(E, none, 0, wt(p->embed.wtq[0]), 64, c.embed_dim, ce, nullptr, nullptr, nullptr, 1, -1, 0);
-      if (p->pipe.fold_embed_output && folded_fwd(g)) {
-        // everything in front of the hidden layer of scalar_embed_mlp folded (fold_embed_output; the forward stored a_e, not the embedding):
-        // d h = ((d[two-body | w0] @ (W1 G0)^T) + d a_e of the moments) x silu'(h) -- ONE 256 -> 64 layer, 8 steps -- ...
-        ca.nlayers = 1;
-        ca.L[0] = chain_layer(E, in, 0, wt(p->o_g0tfq), p->ng0, 64, cn, nullptr, &zz, &ad, 0, 0, 0);
-        if (p->pipe.embed_fused && p->pipe.fold_embed_table) {
-          // ... contracted against the folded two-body table in its epilogue
-          ca.L[0].embrev_out = buf(w.trev);
-          ca.emb_table = wt(p->o_embtab_h);
-          ca.num_types = c.num_types;
-          ca.types = g->types;
-          ca.center = g->center;
-          ca.nbr = g->nbr;
+      case TpPath::General: {
+        TpLayerBwdArgs a{};
+        general_operands(a, g, l);
+        a.gout = l < L - 1 ? buf(w.g_tf[l & 1]) : nullptr;
+        a.gscal = buf(w.g_scal[l]);
+        a.ld_gscal = u;
+        if (l == 0) {
+          a.g1.gw = buf(w.g_w0);
+          a.g1.ldgw = W;
+          a.g1.gsh = buf(w.g_sh);
+          a.g1.ld_gsh = p->D;
         } else {
-          // ... (three species: no table in the chain's LDS) followed by W0^T -> d emb0 for the edge reverse
-          ca.nlayers = 2;
-          ca.L[1] = chain_layer(E, none, 0, wt(p->embed.wtq[0]), 64, c.embed_dim, ce, nullptr, nullptr, nullptr, 1, -1, 0);
+          a.g1.dense = buf(w.g_tf[(l - 1) & 1]);
         }
-      } else if (p->pipe.embed_fused && p->pipe.fold_embed_table) {
-        // folded table (fold_embed_table): d_h, the output of the second layer, is contracted straight back to the 8 basis functions
-        // with T = tab @ W0 -- the layer W0^T and d emb0 do not exist
-        ca.nlayers = 2;
-        ca.L[1].embrev_out = buf(w.trev);
-        ca.emb_table = wt(p->o_embtab_h);
-        ca.num_types = c.num_types;
-        ca.types = g->types;
-        ca.center = g->center;
-        ca.nbr = g->nbr;
-      } else if (p->pipe.embed_fused) {
-        // d emb0 is contracted straight back to the 8 basis functions in the epilogue and never stored
-        ca.L[2].g.c = SegList{1, {seg(nullptr, c.embed_dim, c.embed_dim)}};
-        ca.L[2].embrev_out = buf(w.trev);
-        ca.emb_table = wt(p->o_embtab);
-        ca.num_types = c.num_types;
-        ca.types = g->types;
-        ca.center = g->center;
-        ca.nbr = g->nbr;
+        a.g2.gw = buf(w.g_envw);
+        a.g2.ldgw = W;
+        a.g2.gsh = buf(w.g_sh);
+        a.g2.ld_gsh = p->D;
+        if (int rc = launch_tp_layer_bwd<T>(p->layers[l], a, stream)) return rc;
+        return mark("tp_layer_bwd", 4 * W + 2 * p->D + 2 * u * p->D + u, 2.0 * p->D * u);
       }
-      if (int rc = run_chain(ca, "B1")) return rc;
-    } else {
-    // fused first stage reverse
-    {
-      SegList go{3, {seg(buf(w.g_fcat), SL1, S), seg(buf(w.g_w0), W, W), seg(buf(w.g_envw), W, W)}};
-      if (p->pipe.env_moments()) go.count = 2;
-      SegList gi{1, {seg(buf(w.g_emb), S, S)}};
-      SegList aenv{1, {seg(p->pipe.env_moments() ? buf(w.g_aenv) : nullptr, S, S)}};
-      act_now = AA_ACT_SILU;
-      if (int rc = gemm(go, 0, wt(p->o_g0t), wt(p->o_g0tp), wt(p->o_g0tq), p->ng0, S, gi, nullptr, nullptr,
-                        p->pipe.env_moments() ? &aenv : nullptr))
-        return rc;
     }
-    // scalar_embed_mlp reverse
-    {
+    return fail(AA_ERR_INVALID, "step plan: unknown tensor-product path");
+  }
+
+  // first-stage reverse + scalar_embed_mlp reverse
+  int bwd_first_stage(const aa_graph* g) {
+    const aa_model_config& c = p->cfg;
+    const int S = c.num_scalar, W = p->W, SL1 = p->SL1;
+    if (!p->pipe.chains()) {
+      // fused first stage reverse
+      {
+        SegList go{3, {seg(buf(w.g_fcat), SL1, S), seg(buf(w.g_w0), W, W), seg(buf(w.g_envw), W, W)}};
+        if (p->pipe.env_moments()) go.count = 2;
+        SegList gi{1, {seg(buf(w.g_emb), S, S)}};
+        SegList aenv{1, {seg(p->pipe.env_moments() ? buf(w.g_aenv) : nullptr, S, S)}};
+        act_now = AA_ACT_SILU;
+        if (int rc = gemm(go, 0, wt(p->o_g0t), wt(p->o_g0tp), wt(p->o_g0tq), p->ng0, S, gi, nullptr, nullptr,
+                          p->pipe.env_moments() ? &aenv : nullptr))
+          return rc;
+      }
+      // scalar_embed_mlp reverse
       SegList go{1, {seg(buf(w.g_emb), S, S)}};
       SegList gi{1, {seg(buf(w.g_emb0), c.embed_dim, c.embed_dim)}};
-      if (int rc = mlp_bwd(p->embed, c.embed_mlp_depth + 1, go, w.se_h, w.g_se_h, gi, nullptr, 0)) return rc;
+      return mlp_bwd(p->embed, c.embed_mlp_depth + 1, go, w.se_h, w.g_se_h, gi, nullptr, 0);
     }
+    // ... in ONE kernel
+    const SegList none{0, {}};
+    ChainArgs ca{};
+    ca.nlayers = 3;
+    SegList in{2, {seg(buf(w.g_fcat), SL1, S), seg(buf(w.g_w0), W, W)}};
+    SegList cn{1, {seg(nullptr, 64, 64)}};
+    SegList ad{1, {seg(buf(w.g_aenv), S, S)}};
+    SegList zz{1, {seg(buf(w.se_h[0]), 64, 64)}};
+    SegList ce{1, {seg(buf(w.g_emb0), c.embed_dim, c.embed_dim)}};
+    ca.L[0] = chain_layer(E, in, 0, wt(p->o_g0tq), p->ng0, S, cn, nullptr, nullptr, &ad, 0, 0, 0);
+    ca.L[1] = chain_layer(E, none, 0, wt(p->embed.wtq[1]), S, 64, cn, nullptr, &zz, nullptr, 1, 0, 0);
+    ca.L[2] = chain_layer(E, none, 0, wt(p->embed.wtq[0]), 64, c.embed_dim, ce, nullptr, nullptr, nullptr, 1, -1, 0);
+    // the epilogue that contracts d (two-body embedding) straight back to the 8 basis functions (ModelPipeline::embed_fused)
+    auto contract_embedding = [&](ChainLayer& layer, const T* table) {
+      layer.embrev_out = buf(w.trev);
+      ca.emb_table = table;
+      ca.num_types = c.num_types;
+      ca.types = g->types;
+      ca.center = g->center;
+      ca.nbr = g->nbr;
+    };
+    if (sp.folded_first_stage()) {
+      // everything in front of the hidden layer of scalar_embed_mlp folded (fold_embed_output; the forward stored a_e, not the embedding):
+      // d h = ((d[two-body | w0] @ (W1 G0)^T) + d a_e of the moments) x silu'(h) -- ONE 256 -> 64 layer, 8 steps -- ...
+      ca.nlayers = 1;
+      ca.L[0] = chain_layer(E, in, 0, wt(p->o_g0tfq), p->ng0, 64, cn, nullptr, &zz, &ad, 0, 0, 0);
+      if (p->pipe.embed_fused && p->pipe.fold_embed_table) {
+        // ... contracted against the folded two-body table in its epilogue
+        contract_embedding(ca.L[0], wt(p->o_embtab_h));
+      } else {
+        // ... (three species: no table in the chain's LDS) followed by W0^T -> d emb0 for the edge reverse
+        ca.nlayers = 2;
+        ca.L[1] = chain_layer(E, none, 0, wt(p->embed.wtq[0]), 64, c.embed_dim, ce, nullptr, nullptr, nullptr, 1, -1, 0);
+      }
+    } else if (p->pipe.embed_fused && p->pipe.fold_embed_table) {
+      // folded table (fold_embed_table): d_h, the output of the second layer, is contracted straight back to the 8 basis functions
+      // with T = tab @ W0 -- the layer W0^T and d emb0 do not exist
+      ca.nlayers = 2;
+      contract_embedding(ca.L[1], wt(p->o_embtab_h));
+    } else if (p->pipe.embed_fused) {
+      // d emb0 is contracted straight back to the 8 basis functions in the epilogue and never stored
+      ca.L[2].g.c = SegList{1, {seg(nullptr, c.embed_dim, c.embed_dim)}};
+      contract_embedding(ca.L[2], wt(p->o_embtab));
     }
+    return run_chain(ca, "B1");
+  }
+
+  // The reverse pass w.r.t. positions, top down; the stages the forward of this step already ran (StepPlan::reverse_in_forward)
+  // launch nothing.
+  int backward(const aa_graph* g, const void* pos, void* forces) {
+    if (sp.slot) return backward_slot(g, pos, forces);
+    if (int rc = bwd_begin(forces)) return rc;
+    if (int rc = bwd_readout(g)) return rc;
+    for (int l = p->cfg.num_layers - 1; l >= 0; --l) {
+      if (int rc = bwd_latent(l)) return rc;
+      if (int rc = bwd_tp_layer(g, l)) return rc;
+    }
+    if (int rc = bwd_first_stage(g)) return rc;
     return edge_tail(g, pos, forces);
   }
 };
@@ -2658,7 +2773,19 @@ int run_model(const aa_model_plan* p, const void* dev_weights, const aa_graph* g
   r.w = layout_workspace(p, r.N, r.E, forces != nullptr);
   if (r.w.total > ws_bytes) return fail(AA_ERR_WORKSPACE, "aa_model_energy_forces: workspace too small");
   if (p->opt.poison_workspace) AA_CHECK_HIP(hipMemsetAsync(workspace, 0xFF, r.w.total, stream));  // debugging: NaN everywhere
-  r.want_forces = forces != nullptr;
+  StepInputs in{};
+  in.f32 = sizeof(T) == 4;
+  in.taps = p->taps;
+  in.with_forces = forces != nullptr;
+  in.transposed_csr = g->t_rowptr && g->t_perm;
+  in.atoms = g->num_atoms;
+  in.edges = g->num_edges;
+  in.atom0 = r.atom_begin(g);
+  in.atom_end = r.atom_end(g);
+  in.max_degree = g->max_degree;
+  int cus = 0;  // (asked only where a decision reads it)
+  if (wide_one_tile_pass(p->pipe, choose_forward(p->pipe, p->opt, p->cfg, in)) && (cus = device_cu_count()) < 0) return cus;
+  r.sp = choose_step(p->pipe, p->opt, p->cfg, in, cus);
   if (p->ev_wait) AA_CHECK_HIP(hipStreamWaitEvent(stream, (hipEvent_t)(uintptr_t)(p->ev_wait), 0));
   if (int rc = r.forward(g, pos, atom_energy)) return rc;
   if (p->ev_record) AA_CHECK_HIP(hipEventRecord((hipEvent_t)(uintptr_t)(p->ev_record), stream));
