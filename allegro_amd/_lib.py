@@ -89,6 +89,11 @@ class Graph(C.Structure):
                 ("max_degree", C.c_int64)]
 
 
+class PairZbl(C.Structure):
+    """`aa_pair_zbl`: the ZBL pair potential of a plan (aa_model_plan_set_pair_zbl)."""
+    _fields_ = [("num_types", C.c_int32), ("atomic_numbers", _dp), ("qqr2e", C.c_double), ("poly_p", C.c_double)]
+
+
 class GemmSeg(C.Structure):
     _fields_ = [("p", C.c_void_p), ("ld", C.c_int32), ("n", C.c_int32)]
 
@@ -199,6 +204,8 @@ class AllegroLib:
         L.aa_model_plan_destroy.restype = None
         L.aa_model_plan_set_forward_events.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.aa_model_plan_set_forward_events.restype = C.c_int
+        L.aa_model_plan_set_pair_zbl.argtypes = [C.c_void_p, C.POINTER(PairZbl)]
+        L.aa_model_plan_set_pair_zbl.restype = C.c_int
         L.aa_model_plan_enable_graph.argtypes = [C.c_void_p, C.c_int]
         L.aa_model_plan_enable_graph.restype = C.c_int
         L.aa_model_plan_enable_taps.argtypes = [C.c_void_p, C.c_int]

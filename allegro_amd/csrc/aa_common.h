@@ -791,6 +791,26 @@ int launch_graph_hint_check(const int32_t* rowptr, int64_t N, int64_t a0, int64_
 template <typename T>
 int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t stream);
 
+// ZBL pair potential (nequip.nn.pair_potential.ZBL = LAMMPS pair_style zbl, EXT; hooked in at allegro_models.py:270-288):
+//   E_e = c_ij / r * psi(a_ij r) * f_p(r * rmax_recip[t_i, t_j]),  E_atom[center(e)] += E_e   (not scaled, after scale / shift)
+// and, on a step that computes forces, dvec[e] += dE_e/dr * r_e / r.  r_e comes from pos / nbr / shift_vec: the launch does not
+// depend on what the forward of the step left in the workspace.
+struct PairZblArgs {
+  int64_t atom0, atom_end;  // the active atom block
+  const int32_t *rowptr, *nbr, *types;
+  const void* pos;          // [N,3]
+  const void* shift_vec;    // [E,3] or nullptr
+  int num_types;
+  const void* rmax_recip;   // [T,T] model dtype
+  const double* tab;        // [T*T][2] device: a_ij = (Z_i^0.23 + Z_j^0.23) / 0.46850, c_ij = qqr2e / 2 * Z_i Z_j
+  double poly_p;
+  void* atom_energy;        // [N] accumulated into
+  void* dvec;               // [E,4] accumulated into (every edge owns its row), or nullptr: energy only
+  void* forces;             // [N,3] accumulated into with atomics, or nullptr (forces are gathered from dvec, or not asked for)
+};
+template <typename T>
+int launch_pair_zbl(const PairZblArgs& a, hipStream_t stream);
+
 struct ReadoutArgs {
   int64_t E, N;
   const int32_t *rowptr, *center, *types;

@@ -500,6 +500,95 @@ __global__ __launch_bounds__(256) void force_gather_kernel(ForceGatherArgs a) {
   }
 }
 
+__device__ __forceinline__ float zbl_exp(float x) { return expf(x); }
+__device__ __forceinline__ double zbl_exp(double x) { return aa_exp_f64(x); }
+
+// ZBL pair potential: 8 lanes per center atom walk its segment (one streaming pass: positions, types and, on a force step, the
+// edge's own dvec row); the per-atom energy is summed in a fixed order and added to atom_energy, which the forward has written.
+template <typename T>
+__global__ __launch_bounds__(256) void pair_zbl_kernel(PairZblArgs a) {
+  const int sub = threadIdx.x & 7;
+  const int64_t n = a.atom0 + ((int64_t(blockIdx.x) * 256 + threadIdx.x) >> 3);
+  const T* pos = static_cast<const T*>(a.pos);
+  T en = T(0), fx = T(0), fy = T(0), fz = T(0);
+  int deg = 0;
+  if (n < a.atom_end) {
+    const int beg = a.rowptr[n], end = a.rowptr[n + 1];
+    deg = end - beg;
+    const int ti = a.types[n];
+    const T px = pos[3 * n], py = pos[3 * n + 1], pz = pos[3 * n + 2];
+    for (int64_t e = beg + sub; e < end; e += 8) {
+      const int64_t j = a.nbr[e];
+      T vx = pos[3 * j] - px, vy = pos[3 * j + 1] - py, vz = pos[3 * j + 2] - pz;
+      if (a.shift_vec) {
+        const T* sv = static_cast<const T*>(a.shift_vec) + 3 * e;
+        vx += sv[0];
+        vy += sv[1];
+        vz += sv[2];
+      }
+      const T r = aa_sqrt(vx * vx + vy * vy + vz * vz), inv = T(1) / r;
+      const int cls = ti * a.num_types + a.types[j];
+      const T recip = static_cast<const T*>(a.rmax_recip)[cls];
+      T f, df;
+      cutoff_and_grad<T>(r * recip, T(a.poly_p), f, df);  // (0, 0) from the pair's cutoff on: such an edge adds exactly 0
+      const T ka = T(a.tab[2 * cls]), kc = T(a.tab[2 * cls + 1]);
+      const T y = ka * r;
+      const T e0 = T(0.02817) * zbl_exp(T(-0.20162) * y), e1 = T(0.28022) * zbl_exp(T(-0.40290) * y);
+      const T e2 = T(0.50986) * zbl_exp(T(-0.94229) * y), e3 = T(0.18175) * zbl_exp(T(-3.19980) * y);
+      const T psi = e0 + e1 + e2 + e3;
+      const T dpsi = -ka * (T(0.20162) * e0 + T(0.40290) * e1 + T(0.94229) * e2 + T(3.19980) * e3);  // d psi / d r
+      const T g = kc * inv;
+      en += g * psi * f;
+      if (a.dvec) {
+        const T dEdr = g * ((dpsi - psi * inv) * f + psi * df * recip);
+        const T dx = dEdr * vx * inv, dy = dEdr * vy * inv, dz = dEdr * vz * inv;
+        typedef T V4 __attribute__((ext_vector_type(4)));
+        V4* row = reinterpret_cast<V4*>(static_cast<T*>(a.dvec) + 4 * e);
+        V4 d = *row;
+        d[0] += dx;
+        d[1] += dy;
+        d[2] += dz;
+        *row = d;
+        if (a.forces) {
+          // r_e = pos_j - pos_i: the neighbor gets -d here, the center +sum d below (as edge_backward_kernel)
+          T* F = static_cast<T*>(a.forces);
+          atomicAdd(&F[3 * j], -dx);
+          atomicAdd(&F[3 * j + 1], -dy);
+          atomicAdd(&F[3 * j + 2], -dz);
+          fx += dx;
+          fy += dy;
+          fz += dz;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 4; m >= 1; m >>= 1) {
+    en += __shfl_xor(en, m);
+    fx += __shfl_xor(fx, m);
+    fy += __shfl_xor(fy, m);
+    fz += __shfl_xor(fz, m);
+  }
+  if (deg > 0 && sub == 0) {
+    static_cast<T*>(a.atom_energy)[n] += en;
+    if (a.dvec && a.forces) {
+      T* F = static_cast<T*>(a.forces);
+      atomicAdd(&F[3 * n], fx);
+      atomicAdd(&F[3 * n + 1], fy);
+      atomicAdd(&F[3 * n + 2], fz);
+    }
+  }
+}
+
+template <typename T>
+int launch_pair_zbl(const PairZblArgs& a, hipStream_t stream) {
+  const int64_t n = a.atom_end - a.atom0;
+  if (n <= 0) return AA_OK;
+  hipLaunchKernelGGL(pair_zbl_kernel<T>, dim3((unsigned)((n * 8 + 255) / 256)), dim3(256), 0, stream, a);
+  AA_CHECK_HIP(hipGetLastError());
+  return AA_OK;
+}
+
 // one wave per atom: E_i = scale_t * factor * sum_{e in seg(i)} sum_c act(h[e,c]) w[c] + shift_t
 template <typename T>
 __global__ __launch_bounds__(256) void readout_reduce_kernel(ReadoutArgs a) {
@@ -691,6 +780,7 @@ int launch_readout_backward(const ReadoutArgs& a, hipStream_t stream) {
   template int launch_edge_backward<T>(const EdgeBwdArgs&, hipStream_t);       \
   template int launch_force_gather<T>(const ForceGatherArgs&, hipStream_t);    \
   template int launch_virial<T>(const VirialArgs&, hipStream_t);               \
+  template int launch_pair_zbl<T>(const PairZblArgs&, hipStream_t);            \
   template int launch_readout_reduce<T>(const ReadoutArgs&, hipStream_t);      \
   template int launch_readout_backward<T>(const ReadoutArgs&, hipStream_t);
 AA_INST(float)

@@ -352,6 +352,7 @@ struct StepInputs {
   int64_t atoms, edges;     // of the graph
   int64_t atom0, atom_end;  // the active block: the atom-block hint, or every atom
   int64_t max_degree;       // aa_graph::max_degree, 0 = unknown
+  bool pair_zbl;            // aa_model_plan_set_pair_zbl: the plan carries a ZBL pair potential
 };
 
 enum class ForwardKind {
@@ -388,6 +389,7 @@ struct StepPlan {
   LatentReverse latent_reverse;
   bool gather;                          // deterministic force assembly over the transposed CSR (off: atomics)
   bool zero_gsh, zero_forces;           // the reverse pass accumulates into d Y / the forces: zeroed first
+  bool pair_zbl;                        // ZBL pair potential: one launch behind the forward (energy only) or in edge_tail (force step)
 
   bool fused() const { return forward == ForwardKind::FusedOneTile || forward == ForwardKind::FusedTeam || forward == ForwardKind::FusedMixed; }
   // did the forward of this step leave a_e in the embedding's slot (folded first stage / env weights in the reverse)?
@@ -500,6 +502,7 @@ static StepPlan choose_step(const ModelPipeline& pipe, const aa_plan_options& op
   // spec path with u <= 64 writes every g_sh slot with plain stores; otherwise slots are accumulated into
   s.zero_gsh = in.with_forces && !((pipe.channel_minor() && c.num_tensor <= 64) || pipe.tp_op >= 0);
   s.zero_forces = in.with_forces && !s.gather;
+  s.pair_zbl = in.pair_zbl;
   return s;
 }
 
@@ -576,6 +579,9 @@ struct aa_model_plan {
   // distinct argument set and replayed with one hipGraphLaunch -- for launch-bound (small) systems
   mutable void* ev_wait = nullptr;    // aa_model_plan_set_forward_events
   mutable void* ev_record = nullptr;
+  // ZBL pair potential (aa_model_plan_set_pair_zbl): per-type-pair constants [T*T][2] on the device, immutable until set again
+  double* zbl_tab = nullptr;
+  double zbl_poly_p = 0.0;
   struct StepGraph {
     bool enabled = false;
     hipStream_t cap_stream = nullptr;
@@ -837,12 +843,12 @@ extern "C" int aa_model_plan_describe(const aa_model_plan* p, char* buf, size_t 
   const int k = snprintf(buf, n,
                          "{\"fused_forward\": %s, \"fold_embed_table\": %s, \"fold_embed_output\": %s, \"fold_latent_outputs\": %s, "
                          "\"fold_lat0_reverse\": %s, \"fused_mfma_steps_executed\": %d, \"fused_mfma_steps_reference\": %d, "
-                         "\"chain_gemm\": %s, \"moments\": %s, \"operator_path\": %s, \"slot_form\": %s, \"fused_wide\": %s}",
+                         "\"chain_gemm\": %s, \"moments\": %s, \"operator_path\": %s, \"slot_form\": %s, \"fused_wide\": %s%s}",
                          fused ? "true" : "false", (fused && m.fold_embed_table) ? "true" : "false",
                          (fused && m.fold_embed_output) ? "true" : "false", (fused && m.fold_latent_outputs) ? "true" : "false",
                          m.fold_lat0_reverse ? "true" : "false", exec_steps, fused ? ref_steps : 0, m.chains() ? "true" : "false",
                          m.env_moments() ? "true" : "false", m.tp == TpPath::Operator ? "true" : "false", m.slot() ? "true" : "false",
-                         m.fused_wide ? "true" : "false");
+                         m.fused_wide ? "true" : "false", p->zbl_tab ? ", \"pair\": \"zbl\"" : "");
   return (k < 0 || size_t(k) >= n) ? fail(AA_ERR_INVALID, "aa_model_plan_describe: buffer too small") : k;
 }
 
@@ -856,6 +862,46 @@ extern "C" int aa_model_plan_set_forward_events(aa_model_plan* plan, void* wait_
   AA_REQUIRE(plan, "aa_model_plan_set_forward_events: null plan");
   plan->ev_wait = wait_event;
   plan->ev_record = record_event;
+  return AA_OK;
+}
+
+static void drop_step_graph(aa_model_plan* plan) {
+  aa_model_plan::StepGraph& g = plan->sg;
+  if (g.exec) (void)hipGraphExecDestroy(g.exec);
+  if (g.graph) (void)hipGraphDestroy(g.graph);
+  g.exec = nullptr;
+  g.graph = nullptr;
+}
+
+extern "C" int aa_model_plan_set_pair_zbl(aa_model_plan* plan, const aa_pair_zbl* zbl) {
+  AA_REQUIRE(plan, "aa_model_plan_set_pair_zbl: null plan");
+  double* tab = nullptr;
+  if (zbl) {
+    const int T = plan->cfg.num_types;
+    AA_REQUIRE(zbl->num_types == T, "aa_model_plan_set_pair_zbl: num_types differs from the plan's");
+    AA_REQUIRE(zbl->atomic_numbers, "aa_model_plan_set_pair_zbl: null atomic_numbers");
+    for (int t = 0; t < T; ++t) AA_REQUIRE(zbl->atomic_numbers[t] > 0.0, "aa_model_plan_set_pair_zbl: atomic numbers must be positive");
+    AA_REQUIRE(zbl->qqr2e > 0.0, "aa_model_plan_set_pair_zbl: qqr2e must be positive");
+    AA_REQUIRE(zbl->poly_p > 0.0, "aa_model_plan_set_pair_zbl: poly_p must be positive");
+    std::vector<double> host(size_t(T) * T * 2);
+    for (int i = 0; i < T; ++i)
+      for (int j = 0; j < T; ++j) {
+        const double zi = zbl->atomic_numbers[i], zj = zbl->atomic_numbers[j];
+        host[2 * (size_t(i) * T + j)] = (std::pow(zi, 0.23) + std::pow(zj, 0.23)) / 0.46850;
+        host[2 * (size_t(i) * T + j) + 1] = 0.5 * zbl->qqr2e * zi * zj;
+      }
+    AA_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&tab), host.size() * sizeof(double)));
+    if (hipMemcpy(tab, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(tab);
+      return fail(AA_ERR_HIP, "aa_model_plan_set_pair_zbl: cannot copy the pair table");
+    }
+  }
+  // a captured step belongs to the pair potential that was set when it was captured; steps still in flight read the old table
+  // (hipFree waits for them)
+  drop_step_graph(plan);
+  if (plan->zbl_tab) (void)hipFree(plan->zbl_tab);
+  plan->zbl_tab = tab;
+  plan->zbl_poly_p = zbl ? zbl->poly_p : 0.0;
   return AA_OK;
 }
 
@@ -889,6 +935,7 @@ extern "C" void aa_model_plan_destroy(aa_model_plan* plan) {
   if (plan->sg.graph) (void)hipGraphDestroy(plan->sg.graph);
   if (plan->sg.cap_stream) (void)hipStreamDestroy(plan->sg.cap_stream);
   for (void* q : plan->owned) (void)hipFree(q);
+  if (plan->zbl_tab) (void)hipFree(plan->zbl_tab);
   if (plan->status) (void)hipHostFree(plan->status);
   delete plan;
 }
@@ -1563,6 +1610,7 @@ struct Runner {
   hipStream_t stream;
   StageProfile* prof = nullptr;
   StepPlan sp{};  // the launches of this step (choose_step): set by run_model, read everywhere below
+  void* e_out = nullptr;  // atom_energy of this step (what the pair potential adds to)
 
   // per_edge / per_atom: operand elements the launch must move (each distinct operand row once); see DESIGN.md §5
   int mark(const char* name, double per_edge = 0, double per_atom = 0, double flops = 0) {
@@ -2352,6 +2400,29 @@ struct Runner {
     return fwd_readout(g, atom_energy);
   }
 
+  // ZBL pair potential (StepPlan::pair_zbl): adds to atom_energy, which the forward of this step has written, and -- on a force
+  // step, behind edge_backward -- to the dvec rows (and to the forces where they are not gathered from dvec)
+  int pair_zbl(const aa_graph* g, const void* pos, void* forces) {
+    PairZblArgs a{};
+    a.atom0 = atom_begin(g);
+    a.atom_end = atom_end(g);
+    a.rowptr = g->rowptr;
+    a.nbr = g->nbr;
+    a.types = g->types;
+    a.pos = pos;
+    a.shift_vec = g->shift_vec;
+    a.num_types = p->cfg.num_types;
+    a.rmax_recip = wt(p->o_rmax);
+    a.tab = p->zbl_tab;
+    a.poly_p = p->zbl_poly_p;
+    a.atom_energy = e_out;
+    a.dvec = forces ? buf(w.dvec) : nullptr;
+    a.forces = (forces && !sp.gather) ? forces : nullptr;
+    if (int rc = launch_pair_zbl<T>(a, stream)) return rc;
+    // per edge: neighbor index + its position and type (+ the shift vector), on a force step the dvec row read and written
+    return mark("pair_zbl", 4.0 / sizeof(T) + 3 + 4.0 / sizeof(T) + (g->shift_vec ? 3 : 0) + (forces ? 8 : 0), 2 + 8.0 / sizeof(T));
+  }
+
   // geometry reverse + force assembly (the end of every reverse pass)
   int edge_tail(const aa_graph* g, const void* pos, void* forces) {
     const aa_model_config& c = p->cfg;
@@ -2368,6 +2439,8 @@ struct Runner {
     eb.gather = gather ? 1 : 0;
     if (int rc = launch_edge_backward<T>(eb, stream)) return rc;
     if (int rc = mark("edge_backward", 8.0 / sizeof(T) + 4 + (p->pipe.embed_fused ? c.num_bessels : c.embed_dim) + double(num_gsh) * p->D + (gather ? 4 : 6))) return rc;
+    if (sp.pair_zbl)
+      if (int rc = pair_zbl(g, pos, forces)) return rc;
     if (gather) {
       // deterministic force assembly: per atom, own segment minus transposed segment, fixed order (no atomics)
       ForceGatherArgs fg{N, g->rowptr, g->t_rowptr, g->t_perm, buf(w.dvec), forces};
@@ -2770,6 +2843,7 @@ int run_model(const aa_model_plan* p, const void* dev_weights, const aa_graph* g
   r.E = g->num_edges;
   r.N = g->num_atoms;
   r.stream = stream;
+  r.e_out = atom_energy;
   r.w = layout_workspace(p, r.N, r.E, forces != nullptr);
   if (r.w.total > ws_bytes) return fail(AA_ERR_WORKSPACE, "aa_model_energy_forces: workspace too small");
   if (p->opt.poison_workspace) AA_CHECK_HIP(hipMemsetAsync(workspace, 0xFF, r.w.total, stream));  // debugging: NaN everywhere
@@ -2783,14 +2857,18 @@ int run_model(const aa_model_plan* p, const void* dev_weights, const aa_graph* g
   in.atom0 = r.atom_begin(g);
   in.atom_end = r.atom_end(g);
   in.max_degree = g->max_degree;
+  in.pair_zbl = p->zbl_tab != nullptr;
   int cus = 0;  // (asked only where a decision reads it)
   if (wide_one_tile_pass(p->pipe, choose_forward(p->pipe, p->opt, p->cfg, in)) && (cus = device_cu_count()) < 0) return cus;
   r.sp = choose_step(p->pipe, p->opt, p->cfg, in, cus);
   if (p->ev_wait) AA_CHECK_HIP(hipStreamWaitEvent(stream, (hipEvent_t)(uintptr_t)(p->ev_wait), 0));
   if (int rc = r.forward(g, pos, atom_energy)) return rc;
   if (p->ev_record) AA_CHECK_HIP(hipEventRecord((hipEvent_t)(uintptr_t)(p->ev_record), stream));
-  if (forces)
-    if (int rc = r.backward(g, pos, forces)) return rc;
+  if (forces) {
+    if (int rc = r.backward(g, pos, forces)) return rc;  // (ends in edge_tail, which launches the pair potential of a force step)
+  } else if (r.sp.pair_zbl) {
+    if (int rc = r.pair_zbl(g, pos, nullptr)) return rc;
+  }
   // the atom-block hint is the caller's promise (per-atom kernels skip the rest): two row pointers verify it on the device, as the
   // LAST launch of the step, so that a broken promise also turns this step's energies and forces into NaN
   if (g->atom_end > g->atom_begin && (g->atom_begin > 0 || g->atom_end < g->num_atoms) && p->status)

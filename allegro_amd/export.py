@@ -33,9 +33,17 @@ def _bits(x: float) -> int:
     return struct.unpack("<q", struct.pack("<d", float(x)))[0]
 
 
+def _refuse_pair_potential(model) -> None:
+    # (the config word list, the host-file format and aa_model_config have no field for it: a host would silently run without the core repulsion)
+    if getattr(model, "pair_zbl", None) is not None:
+        raise NotImplementedError("pair_potential (ZBL) is not carried by the exported config / host model file: such a model runs "
+                                  "through HipAllegroModel, or a C host calls aa_model_plan_set_pair_zbl itself")
+
+
 def serialize_config(model, layout_hash: int = 0) -> list:
     """`aa_model_config` of a HipAllegroModel as the int64 word list torch_ops.cpp parses; `layout_hash` is the digest of
     the blob layout the weights were packed for (aa_model_plan_layout_hash; mandatory: the op refuses 0)."""
+    _refuse_pair_potential(model)
     cfg, _keep = model._plan_keep if getattr(model, "_plan_keep", None) else model._build_config()  # (no library call: works without a GPU)
     w = [_MAGIC, cfg.dtype, cfg.num_types, cfg.num_bessels, cfg.l_max, cfg.num_layers, cfg.num_scalar, cfg.num_tensor,
          cfg.embed_dim, cfg.embed_mlp_depth, cfg.embed_mlp_width, cfg.latent_mlp_depth, cfg.latent_mlp_width,
@@ -84,6 +92,7 @@ class ExportableAllegro(torch.nn.Module):
 
     def __init__(self, model, device):
         super().__init__()
+        _refuse_pair_potential(model)
         load_native_ops()
         device = torch.device(device)
         model._select_device(device)

@@ -553,11 +553,40 @@ def neighbor_list(pos: torch.Tensor, cell, pbc, r_cut: float, lib: Optional[_lib
     return DeviceNeighborList(edge_index, rowptr, cell_shift, shift_vec, lib)
 
 
+ZBL_QQR2E = {"metal": 14.399645, "real": 332.06371}  # LAMMPS' qqr2e: eV Angstrom / kcal/mol Angstrom per squared elementary charge
+
+
+def parse_pair_potential(pair_potential: dict, type_names: Sequence[str], poly_p: float) -> dict:
+    """The `pair_potential` constructor argument (allegro_models.py:270-288) -> what `aa_model_plan_set_pair_zbl` takes:
+    {"atomic_numbers": [Z per type], "qqr2e", "poly_p"}.  Only nequip's ZBL module (EXT) exists here."""
+    from ._periodic import ATOMIC_NUMBERS
+
+    cfg = dict(pair_potential)
+    tgt = cfg.pop("_target_", None)
+    if tgt != "nequip.nn.pair_potential.ZBL":
+        raise NotImplementedError(f"pair_potential {tgt!r}: only nequip.nn.pair_potential.ZBL is implemented")
+    units = cfg.pop("units", None)
+    if units not in ZBL_QQR2E:
+        raise ValueError(f"pair_potential units {units!r}: one of {sorted(ZBL_QQR2E)}")
+    species = cfg.pop("chemical_species", None)
+    if species is None or isinstance(species, str) or len(species) != len(type_names):
+        raise ValueError(f"pair_potential chemical_species {species!r}: one chemical symbol per entry of type_names "
+                         f"({len(type_names)}: {list(type_names)})")
+    unknown = [s for s in species if s not in ATOMIC_NUMBERS]
+    if unknown:
+        raise ValueError(f"pair_potential chemical_species: {unknown} are not chemical symbols")
+    cfg.pop("type_names", None)  # (nequip passes the model's own list along)
+    if cfg:
+        raise ValueError(f"pair_potential: unknown arguments {sorted(cfg)}")
+    return dict(atomic_numbers=[float(ATOMIC_NUMBERS[s]) for s in species], qqr2e=ZBL_QQR2E[units], poly_p=float(poly_p))
+
+
 class HipAllegroModel(torch.nn.Module):
     """Energy + forces of an Allegro model through the HIP hot path.
 
-    Constructor arguments follow `allegro.model.AllegroModel` (allegro_models.py:112-147); only the
-    Bessel two-body embedding (`allegro.nn.TwoBodyBesselScalarEmbed`) and SiLU MLPs are supported.
+    Constructor arguments follow `allegro.model.AllegroModel` (allegro_models.py:112-147): both two-body embeddings
+    (`allegro.nn.TwoBodyBesselScalarEmbed`, `allegro.nn.TwoBodySplineScalarEmbed`), the reference's nonlinearities (silu, mish,
+    gelu, None) and, as `pair_potential`, nequip's ZBL core repulsion (`nequip.nn.pair_potential.ZBL`).
     """
 
     def __init__(self, *, type_names: Sequence[str], r_max: float, l_max: int, num_layers: int = 2,
@@ -583,8 +612,6 @@ class HipAllegroModel(torch.nn.Module):
         if bessel_convention not in _BESSEL_CONVENTIONS:
             raise ValueError(f"bessel_convention {bessel_convention!r}: one of {sorted(_BESSEL_CONVENTIONS)}")
         self.bessel_convention = bessel_convention
-        if pair_potential is not None:
-            raise NotImplementedError("pair potentials (nequip's ZBL module, EXT) are outside the hot path (DESIGN.md section 8)")
         self.nonlinearities = (scalar_embed_mlp_nonlinearity, allegro_mlp_nonlinearity, readout_mlp_nonlinearity)
         for nl in self.nonlinearities:
             if nl not in ACT_KINDS:
@@ -616,6 +643,10 @@ class HipAllegroModel(torch.nn.Module):
                             readout_depth=readout_mlp_hidden_layers_depth, readout_width=readout_mlp_hidden_layers_width,
                             coupling=bool(tp_path_channel_coupling), avg_num_neighbors=float(avg_num_neighbors),
                             forward_normalize=bool(forward_normalize), parity=bool(parity))
+        # pair potential (allegro_models.py:270-288): added to the per-atom energies after the per-type scale / shift; its envelope is
+        # the embedding's polynomial cutoff, p = 6 with the spline embedding, which has none (:272-280).  No parameters, no buffers.
+        self.pair_zbl = None if pair_potential is None else parse_pair_potential(
+            pair_potential, self.type_names, self.hparams["poly_p"] if self.embed_kind == 0 else 6.0)
         if seed is not None:
             torch.manual_seed(seed)
         dt = self.dtype
@@ -819,6 +850,19 @@ class HipAllegroModel(torch.nn.Module):
         cfg, keep = self._build_config()
         self._plan_handle = self._get_lib().model_plan_create(cfg)
         self._plan_keep = (cfg, keep)
+        if self.pair_zbl is not None:
+            self.set_pair_zbl(self.pair_zbl)
+
+    def set_pair_zbl(self, zbl: Optional[dict]) -> None:
+        """`aa_model_plan_set_pair_zbl` on the plan of the current device: `zbl` as `parse_pair_potential` returns it, or None to
+        remove the term from that plan (A/B, tests; the model's own setting is applied whenever a plan is created)."""
+        lib = self._get_lib()
+        self._ensure_plan()
+        arg = None
+        if zbl is not None:
+            z = (C.c_double * len(zbl["atomic_numbers"]))(*zbl["atomic_numbers"])
+            arg = C.byref(_lib.PairZbl(len(zbl["atomic_numbers"]), z, zbl["qqr2e"], zbl["poly_p"]))
+        lib.check(lib.lib.aa_model_plan_set_pair_zbl(self._plan_handle, arg), "aa_model_plan_set_pair_zbl")
 
     def _build_config(self):
         """(`aa_model_config`, keep-alive list) of this model: hyper-parameters + the Clebsch-Gordan non-zeros of every layer.
@@ -929,6 +973,17 @@ class HipAllegroModel(torch.nn.Module):
         return blob
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        # the pair potential holds no state here; a checkpoint that carries entries of such a module is accepted, and its atomic
+        # numbers, where present, must be the configured species
+        pair = {k: v for k, v in state_dict.items() if k.startswith(("pair_potential.", "func.pair_potential."))}
+        if pair:
+            state_dict = {k: v for k, v in state_dict.items() if k not in pair}
+            for k, v in pair.items():
+                if k.endswith("pair_potential.atomic_numbers"):
+                    have = None if self.pair_zbl is None else [int(z) for z in self.pair_zbl["atomic_numbers"]]
+                    if have != [int(z) for z in torch.as_tensor(v).reshape(-1).tolist()]:
+                        raise ValueError(f"{k} = {torch.as_tensor(v).reshape(-1).tolist()} in the state_dict, but the model's "
+                                         f"pair_potential is configured for atomic numbers {have}")
         out = super().load_state_dict(state_dict, strict=strict, **kw)
         # w3j buffers may have changed: rebuild device tables lazily
         self._drop_device_state()

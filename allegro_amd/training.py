@@ -257,7 +257,28 @@ class TrainingEvaluator:
             e_atom = e_atom * self._param("per_type_energy_scale_shift.scales").index_select(0, types).reshape(-1, 1)
         if m.has_shifts:
             e_atom = e_atom + self._param("per_type_energy_scale_shift.shifts").index_select(0, types).reshape(-1, 1)
+        if m.pair_zbl is not None:
+            e_atom = e_atom + self._pair_zbl(vec.norm(dim=-1), tc, tn, center, N)
         return e_atom
+
+    def _pair_zbl(self, r: torch.Tensor, tc: torch.Tensor, tn: torch.Tensor, center: torch.Tensor, N: int) -> torch.Tensor:
+        """[N,1] ZBL core repulsion (nequip.nn.pair_potential.ZBL, EXT; allegro_models.py:270-288), the formula of
+        `pair_zbl_kernel` (csrc/aa_edge.hip) as differentiable elementwise operations over the edges: no parameters, but the
+        forces of a force-matching loss differentiate through it."""
+        z = self.model.pair_zbl
+        Z = torch.tensor(z["atomic_numbers"], dtype=torch.float64, device=r.device)
+        zp = Z.pow(0.23)
+        a = ((zp[:, None] + zp[None, :]) / 0.46850).to(r.dtype)
+        c = (0.5 * z["qqr2e"] * Z[:, None] * Z[None, :]).to(r.dtype)
+        recip = self._param("edge_norm.rmax_recip")
+        x = r * (recip[tc, tn] if recip.numel() > 1 else recip.reshape(-1)[0])
+        p = z["poly_p"]
+        cut = 1.0 - ((p + 1) * (p + 2) / 2) * x ** p + p * (p + 2) * x ** (p + 1) - (p * (p + 1) / 2) * x ** (p + 2)
+        y = a[tc, tn] * r
+        psi = (0.02817 * torch.exp(-0.20162 * y) + 0.28022 * torch.exp(-0.40290 * y) + 0.50986 * torch.exp(-0.94229 * y)
+               + 0.18175 * torch.exp(-3.19980 * y))
+        e_edge = c[tc, tn] / r * psi * (cut * (x < 1.0))
+        return torch.zeros((N, 1), dtype=r.dtype, device=r.device).index_add(0, center, e_edge.unsqueeze(-1))
 
     def forward(self, data: Dict[str, torch.Tensor], graph) -> Dict[str, torch.Tensor]:
         """AtomicDataDict out with `forces` (and `stress` / `virial` when `cell` is given) that stay attached to the

@@ -326,6 +326,21 @@ int aa_model_plan_enable_graph(aa_model_plan* plan, int on);
  * i-1's record_event the forwards of consecutive blocks run one after the other while each block's reverse pass overlaps the next
  * block's forward (tools/pipeline_probe.py).  Persistent until set again; not captured by aa_model_plan_enable_graph. */
 int aa_model_plan_set_forward_events(aa_model_plan* plan, void* wait_event, void* record_event);
+/* ZBL pair potential (nequip.nn.pair_potential.ZBL = LAMMPS pair_style zbl, EXT; the `pair_potential` hook of
+ * allegro/model/allegro_models.py:270-288).  Every step on the plan then adds, for every directed edge i -> j,
+ *   E_e = (qqr2e / 2) Z_i Z_j / r * psi((Z_i^0.23 + Z_j^0.23) r / 0.46850) * f_p(r * rmax_recip[t_i, t_j])
+ * to the energy of the edge's center atom (after the per-type scale and shift, unscaled) and dE_e/dr along the edge to the
+ * forces and the strain derivative; f_p is the polynomial cutoff envelope with exponent `poly_p` on the model's own per-type-pair
+ * cutoffs.  atomic_numbers: [num_types] host array, one Z per atom type; qqr2e: 14.399645 (metal units: eV, Angstrom) or 332.06371
+ * (real units: kcal/mol, Angstrom).  NULL removes the pair potential.  AA_ERR_INVALID for a num_types other than the plan's, a
+ * non-positive Z, qqr2e or poly_p.  Persistent until set again; a captured step graph (aa_model_plan_enable_graph) is dropped. */
+typedef struct {
+  int32_t num_types;
+  const double* atomic_numbers; /* [num_types], host */
+  double qqr2e;
+  double poly_p;
+} aa_pair_zbl;
+int aa_model_plan_set_pair_zbl(aa_model_plan* plan, const aa_pair_zbl* zbl);
 /* on != 0: every step materialises the per-edge intermediates that aa_model_debug_tap exposes (the staged pipeline is
  * used; the fused kernels keep them on chip).  Parity tests only. */
 int aa_model_plan_enable_taps(aa_model_plan* plan, int on);
