@@ -785,6 +785,19 @@ struct ForceGatherArgs {
 };
 template <typename T>
 int launch_force_gather(const ForceGatherArgs& a, hipStream_t stream);
+// per-atom strain derivative (index convention of VirialArgs: W[a][b] = sum d[e][a] * r_e[b]), gathered in a fixed order:
+//   out[n] = c_center * sum_{e in seg(n)} d[e] (x) r_e + c_neighbor * sum_{e: nbr(e) = n} d[e] (x) r_e
+// over ALL N atoms.  (1, 0): dE_n/d(strain); (0, 1): the tensor of the heat flux; (1/2, 1/2): the tally of a pair style.
+struct AtomVirialArgs {
+  int64_t N;
+  const int32_t *rowptr, *t_rowptr, *t_perm;  // t_rowptr / t_perm are read only when c_neighbor != 0
+  const void* dvec;  // [E,4]
+  const void* vec;   // [E,4] unit vector, length
+  double c_center, c_neighbor;  // a pass whose coefficient is 0 is skipped
+  void* out;         // [N,9] model dtype, 3x3 row-major per atom
+};
+template <typename T>
+int launch_atom_virial(const AtomVirialArgs& a, hipStream_t stream);
 // verifies the aa_graph.atom_begin / atom_end promise (no edge segment outside the block): *status = -2 otherwise
 int launch_graph_hint_check(const int32_t* rowptr, int64_t N, int64_t a0, int64_t a1, int32_t* status, void* atom_energy, void* forces,
                             int esize, hipStream_t stream);

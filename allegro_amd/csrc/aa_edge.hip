@@ -500,6 +500,49 @@ __global__ __launch_bounds__(256) void force_gather_kernel(ForceGatherArgs a) {
   }
 }
 
+// w += c * d[e] (x) r_e, both [E,4] rows loaded whole (one 16-byte load each in fp32, two in fp64)
+template <typename T>
+__device__ __forceinline__ void atom_virial_edge(const T* dv, const T* vc, int64_t e, double c, double (&w)[9]) {
+  typedef T V4 __attribute__((ext_vector_type(4)));
+  const V4 d = *reinterpret_cast<const V4*>(dv + 4 * e);
+  const V4 v = *reinterpret_cast<const V4*>(vc + 4 * e);
+  const double r = double(v[3]);
+  const double rx = double(v[0]) * r, ry = double(v[1]) * r, rz = double(v[2]) * r;
+  const double dx = c * double(d[0]), dy = c * double(d[1]), dz = c * double(d[2]);
+  w[0] += dx * rx; w[1] += dx * ry; w[2] += dx * rz;
+  w[3] += dy * rx; w[4] += dy * ry; w[5] += dy * rz;
+  w[6] += dz * rx; w[7] += dz * ry; w[8] += dz * rz;
+}
+
+// per-atom strain derivative: 8 lanes per atom walk its own segment (contiguous rows) and its transposed segment (rows gathered
+// through t_perm) in a fixed order, sums in double (as virial_partial_kernel); no atomics
+template <typename T>
+__global__ __launch_bounds__(256) void atom_virial_kernel(AtomVirialArgs a) {
+  const int sub = threadIdx.x & 7;
+  const int64_t n = (int64_t(blockIdx.x) * 256 + threadIdx.x) >> 3;
+  double w[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) w[k] = 0.0;
+  if (n < a.N) {
+    const T* dv = static_cast<const T*>(a.dvec);
+    const T* vc = static_cast<const T*>(a.vec);
+    if (a.c_center != 0.0)
+      for (int e = a.rowptr[n] + sub; e < a.rowptr[n + 1]; e += 8) atom_virial_edge<T>(dv, vc, e, a.c_center, w);
+    if (a.c_neighbor != 0.0)
+      for (int k = a.t_rowptr[n] + sub; k < a.t_rowptr[n + 1]; k += 8) atom_virial_edge<T>(dv, vc, a.t_perm[k], a.c_neighbor, w);
+  }
+#pragma unroll
+  for (int m = 4; m >= 1; m >>= 1) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) w[k] += __shfl_xor(w[k], m);
+  }
+  if (n < a.N && sub == 0) {
+    T* o = static_cast<T*>(a.out) + 9 * n;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) o[k] = T(w[k]);
+  }
+}
+
 __device__ __forceinline__ float zbl_exp(float x) { return expf(x); }
 __device__ __forceinline__ double zbl_exp(double x) { return aa_exp_f64(x); }
 
@@ -734,6 +777,14 @@ int launch_force_gather(const ForceGatherArgs& a, hipStream_t stream) {
   return AA_OK;
 }
 
+template <typename T>
+int launch_atom_virial(const AtomVirialArgs& a, hipStream_t stream) {
+  if (a.N == 0) return AA_OK;
+  hipLaunchKernelGGL(atom_virial_kernel<T>, dim3((unsigned)((a.N * 8 + 255) / 256)), dim3(256), 0, stream, a);
+  AA_CHECK_HIP(hipGetLastError());
+  return AA_OK;
+}
+
 // Runs LAST in a step that carries an atom-block hint.  Edges whose center lies outside [a0, a1) were skipped by every
 // per-atom kernel, so the step's outputs are not the model's: besides raising the status word (reported by the next call /
 // aa_model_check) the outputs of THIS step are overwritten with NaN -- a host that integrates the forces before it looks at
@@ -780,6 +831,7 @@ int launch_readout_backward(const ReadoutArgs& a, hipStream_t stream) {
   template int launch_edge_backward<T>(const EdgeBwdArgs&, hipStream_t);       \
   template int launch_force_gather<T>(const ForceGatherArgs&, hipStream_t);    \
   template int launch_virial<T>(const VirialArgs&, hipStream_t);               \
+  template int launch_atom_virial<T>(const AtomVirialArgs&, hipStream_t);      \
   template int launch_pair_zbl<T>(const PairZblArgs&, hipStream_t);            \
   template int launch_readout_reduce<T>(const ReadoutArgs&, hipStream_t);      \
   template int launch_readout_backward<T>(const ReadoutArgs&, hipStream_t);

@@ -2963,6 +2963,29 @@ extern "C" int aa_model_virial(const aa_model_plan* plan, const aa_graph* graph,
   return plan->cfg.dtype == AA_F32 ? launch_virial<float>(a, s) : launch_virial<double>(a, s);
 }
 
+extern "C" int aa_model_atom_virial(const aa_model_plan* plan, const aa_graph* graph, void* workspace, size_t workspace_bytes,
+                                    int attribution, void* out_n9, aa_stream stream) {
+  AA_REQUIRE(plan && graph && workspace && out_n9, "aa_model_atom_virial: null argument");
+  double cc, cn;
+  switch (attribution) {
+    case AA_ATOM_VIRIAL_CENTER: cc = 1.0, cn = 0.0; break;
+    case AA_ATOM_VIRIAL_NEIGHBOR: cc = 0.0, cn = 1.0; break;
+    case AA_ATOM_VIRIAL_SPLIT: cc = cn = 0.5; break;
+    default: return fail(AA_ERR_INVALID, "aa_model_atom_virial: unknown attribution " + std::to_string(attribution) +
+                                             " (AA_ATOM_VIRIAL_CENTER, _NEIGHBOR or _SPLIT)");
+  }
+  // (no atomics fallback: a per-atom tensor that changes from call to call is what this entry point exists to avoid)
+  if (cn != 0.0 && !(graph->t_rowptr && graph->t_perm))
+    return fail(AA_ERR_INVALID, "aa_model_atom_virial: the neighbor and split attributions need the transposed CSR "
+                                "(aa_graph.t_rowptr / t_perm, aa_graph_transpose)");
+  const Workspace w = layout_workspace(plan, graph->num_atoms, graph->num_edges, 1);
+  if (w.total > workspace_bytes) return fail(AA_ERR_WORKSPACE, "aa_model_atom_virial: workspace too small (was it sized with forces?)");
+  char* base = static_cast<char*>(workspace);
+  AtomVirialArgs a{graph->num_atoms, graph->rowptr, graph->t_rowptr, graph->t_perm, base + w.dvec, base + w.vec, cc, cn, out_n9};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return plan->cfg.dtype == AA_F32 ? launch_atom_virial<float>(a, s) : launch_atom_virial<double>(a, s);
+}
+
 extern "C" int aa_model_debug_tap(const aa_model_plan* plan, const char* name, int64_t N, int64_t E, const void* workspace,
                                   const void** ptr, int64_t* ld) {
   AA_REQUIRE(plan && name && workspace && ptr && ld, "aa_model_debug_tap: null argument");

@@ -1068,6 +1068,37 @@ class HipAllegroModel(torch.nn.Module):
                                           out.data_ptr(), _stream_ptr(out)), "aa_model_virial")
         return out.view(3, 3)
 
+    _ATOM_VIRIAL = {"center": 0, "neighbor": 1, "split": 2}  # AA_ATOM_VIRIAL_*
+
+    def atom_virial(self, graph: PreparedGraph, attribution: str = "center") -> torch.Tensor:
+        """Per-atom dE/d(strain) [N,3,3] of the LAST `energy_forces(..., with_forces=True)` call on `graph`
+        (`aa_model_atom_virial`), W_n[a][b] = sum_e (dE/dr_e)_a (r_e)_b over the edges attributed to atom n:
+        "center": the edges of its own segment (= dE_n/d(strain)); "neighbor": the edges that point at it (the tensor of the
+        heat flux, `heat_flux_potential`); "split": the mean of the two (a pair style's tally).  Not symmetric atom by atom; each
+        sums over the atoms to `virial(graph)`.  Ghost rows carry their own neighbor share.  Bit-reproducible; "neighbor" and
+        "split" need the graph's transposed CSR."""
+        if attribution not in self._ATOM_VIRIAL:
+            raise ValueError(f"attribution must be one of {sorted(self._ATOM_VIRIAL)}, not {attribution!r}")
+        lib = self._get_lib()
+        if getattr(self, "_plan_handle", None) is None or self._workspace is None:
+            raise RuntimeError("atom_virial reads what a step with forces left behind: call energy_forces first")
+        out = torch.empty((graph.num_atoms, 3, 3), dtype=self.dtype, device=self._workspace.device)
+        g = graph.c_struct()
+        with _device_ctx(out.device):
+            lib.check(lib.lib.aa_model_atom_virial(self._plan_handle, C.byref(g), self._workspace.data_ptr(), self._workspace.numel(),
+                                                   self._ATOM_VIRIAL[attribution], out.data_ptr(), _stream_ptr(out)),
+                      "aa_model_atom_virial")
+        return out
+
+    def heat_flux_potential(self, graph: PreparedGraph, velocities: torch.Tensor) -> torch.Tensor:
+        """Potential part of the Green-Kubo heat flux [3] of the last step with forces on `graph`:
+        J_pot[b] = -sum_e (r_e)_b (dE/dr_e . v_j(e)) = -sum_n sum_a v_n[a] Wn_n[a][b], Wn = atom_virial(graph, "neighbor").
+        `velocities`: [N,3] (ghost rows carry the velocity of their source atom).  The convective part sum_n E_n v_n is the caller's."""
+        if tuple(velocities.shape) != (graph.num_atoms, 3):
+            raise ValueError(f"velocities must be [{graph.num_atoms}, 3], not {list(velocities.shape)}")
+        wn = self.atom_virial(graph, "neighbor")
+        return -torch.einsum("na,nab->b", velocities.to(wn), wn)
+
     def enable_hip_graph(self, on: bool = True) -> None:
         """Capture the step's launch sequence into a hipGraph and replay it (aa_model_plan_enable_graph): for
         launch-bound small systems in MD loops.  `pos` must then be updated in place between calls."""

@@ -393,6 +393,23 @@ int aa_model_energy_forces_profiled(const aa_model_plan* plan, const void* dev_w
 int aa_model_virial(const aa_model_plan* plan, const aa_graph* graph, void* workspace, size_t workspace_bytes,
                     void* virial9, aa_stream stream);
 
+/* The same strain derivative atom by atom, from the same two per-edge buffers (call it after a step with forces, like
+ * aa_model_virial; the same workspace check).  Edge e has center i(e) and neighbor j(e), g_e = dE/dr_e, r_e as above:
+ *   AA_ATOM_VIRIAL_CENTER    Wc_n = sum_{e in seg(n)} g_e (x) r_e    = dE_n/d eps (every E_n depends on its own edges only)
+ *   AA_ATOM_VIRIAL_NEIGHBOR  Wn_n = sum_{e: j(e) = n} g_e (x) r_e    the tensor of the Green-Kubo heat flux: with
+ *                            F_n = sum_seg g - sum_nbr g,  J_pot[b] = -sum_n sum_a v_n[a] Wn_n[a][b]  (the convective part
+ *                            sum_n E_n v_n stays with the caller)
+ *   AA_ATOM_VIRIAL_SPLIT     (Wc_n + Wn_n) / 2                       the half-and-half tally of a pair style
+ * out_n9: [num_atoms, 3, 3] row-major, model dtype, device memory, written for ALL atoms whatever atom_begin / atom_end say;
+ * W[a][b] = sum (g_e)_a (r_e)_b, all 9 components (a single atom's tensor is not symmetric).  Each attribution sums over n to
+ * what aa_model_virial returns.  Atoms without edges get zeros; ghost rows (pair_allegro layout) get their own Wn share and a
+ * zero Wc, the rule of the forces.  Sums run in double in a fixed order without atomics: the result is bit-reproducible.
+ * NEIGHBOR and SPLIT gather through aa_graph.t_rowptr / t_perm and return AA_ERR_INVALID without them (no atomics fallback);
+ * so does an unknown attribution.  One launch of its own: not part of the step, of its captured graph or of its profile. */
+enum { AA_ATOM_VIRIAL_CENTER = 0, AA_ATOM_VIRIAL_NEIGHBOR = 1, AA_ATOM_VIRIAL_SPLIT = 2 };
+int aa_model_atom_virial(const aa_model_plan* plan, const aa_graph* graph, void* workspace, size_t workspace_bytes,
+                         int attribution, void* out_n9, aa_stream stream);
+
 /* debug/parity taps: copy an intermediate of the LAST call out of the workspace layout.
  * name in {"edge_attrs","edge_embedding","edge_features","emb0","vec"}; a "+f" suffix selects the workspace layout of
  * a step that computed forces (required for "dvec": dE/dr_e [E,4]); returns elements per edge or <0 */
