@@ -2975,7 +2975,8 @@ extern "C" int aa_model_atom_virial(const aa_model_plan* plan, const aa_graph* g
                                              " (AA_ATOM_VIRIAL_CENTER, _NEIGHBOR or _SPLIT)");
   }
   // (no atomics fallback: a per-atom tensor that changes from call to call is what this entry point exists to avoid)
-  if (cn != 0.0 && !(graph->t_rowptr && graph->t_perm))
+  // (a list without edges has row pointers and an EMPTY t_perm, which a host may well pass as a null pointer: nothing reads it)
+  if (cn != 0.0 && !(graph->t_rowptr && (graph->t_perm || graph->num_edges == 0)))
     return fail(AA_ERR_INVALID, "aa_model_atom_virial: the neighbor and split attributions need the transposed CSR "
                                 "(aa_graph.t_rowptr / t_perm, aa_graph_transpose)");
   const Workspace w = layout_workspace(plan, graph->num_atoms, graph->num_edges, 1);

@@ -404,8 +404,8 @@ int aa_model_virial(const aa_model_plan* plan, const aa_graph* graph, void* work
  * W[a][b] = sum (g_e)_a (r_e)_b, all 9 components (a single atom's tensor is not symmetric).  Each attribution sums over n to
  * what aa_model_virial returns.  Atoms without edges get zeros; ghost rows (pair_allegro layout) get their own Wn share and a
  * zero Wc, the rule of the forces.  Sums run in double in a fixed order without atomics: the result is bit-reproducible.
- * NEIGHBOR and SPLIT gather through aa_graph.t_rowptr / t_perm and return AA_ERR_INVALID without them (no atomics fallback);
- * so does an unknown attribution.  One launch of its own: not part of the step, of its captured graph or of its profile. */
+ * NEIGHBOR and SPLIT gather through aa_graph.t_rowptr / t_perm and return AA_ERR_INVALID without them (no atomics fallback;
+ * t_perm may be NULL where num_edges is 0); so does an unknown attribution.  One launch of its own: not part of the step, of its captured graph or of its profile. */
 enum { AA_ATOM_VIRIAL_CENTER = 0, AA_ATOM_VIRIAL_NEIGHBOR = 1, AA_ATOM_VIRIAL_SPLIT = 2 };
 int aa_model_atom_virial(const aa_model_plan* plan, const aa_graph* graph, void* workspace, size_t workspace_bytes,
                          int attribution, void* out_n9, aa_stream stream);

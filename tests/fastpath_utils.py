@@ -45,6 +45,23 @@ def _dense_cluster(n=40, seed=9):
     return pos, cell, ei[:, keep], shift[keep], rng.integers(0, 2, size=n + 1)
 
 
+def oracle64_errors(got, w32, w64):
+    """(err_hip, err_cpu32, scale) of the fp32 criterion: the distance of the fp32 result `got` and of the fp32 CPU oracle `w32`
+    from the fp64 oracle on the same (upcast) weights `w64`, and the output scale max(1, max |w64|)."""
+    scale = max(1.0, float(w64.abs().max())) if w64.numel() else 1.0
+    err_hip = (got.double() - w64).abs().max().item() if w64.numel() else 0.0
+    err_cpu32 = (w32.double() - w64).abs().max().item() if w64.numel() else 0.0
+    return err_hip, err_cpu32, scale
+
+
+def assert_vs_oracle64(got, w32, w64, what=""):
+    """HIP fp32 may not be further from the fp64 oracle than the fp32 CPU oracle is, x2 + a floor of 1e-5 of the output scale."""
+    assert torch.isfinite(got).all(), what
+    err_hip, err_cpu32, scale = oracle64_errors(got, w32, w64)
+    assert err_hip <= 2.0 * err_cpu32 + 1e-5 * scale, (what, err_hip, err_cpu32, scale)
+    return err_hip, err_cpu32, scale
+
+
 def _vs_oracle64(cfg, pos, cell, ei, shift, types, lib, dev):
     """HIP fp32 may not be further from the fp64 oracle on the same (upcast) weights than the fp32 CPU oracle is
     (x2 + a small floor) -- the criterion of tests/test_hip_model.py for fp32 sums."""
@@ -65,13 +82,8 @@ def _vs_oracle64(cfg, pos, cell, ei, shift, types, lib, dev):
     ref64 = R.allegro_energy_forces(dict(cfg, model_dtype="float64"), sd64, torch.tensor(pos), torch.tensor(ei), tt, sv.double())
     for got, w32, w64 in ((e, ref32["atomic_energy"].reshape(-1), ref64["atomic_energy"].reshape(-1)),
                           (f, ref32["forces"], ref64["forces"])):
-        assert torch.isfinite(got).all()
-        scale = max(1.0, float(w64.abs().max()))
-        err_hip = (got.double() - w64).abs().max().item()
-        err_cpu32 = (w32.double() - w64).abs().max().item()
-        assert err_hip <= 2.0 * err_cpu32 + 1e-5 * scale, (err_hip, err_cpu32, scale)
+        assert_vs_oracle64(got, w32, w64)
     return m
-
 
 
 def _assert_launched(m, pos, cell, ei, shift, types, present, absent):
