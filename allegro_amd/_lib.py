@@ -138,6 +138,16 @@ class NlInput(C.Structure):
                 ("dtype", C.c_int32), ("r_cut", C.c_double)]
 
 
+class NlTypes(C.Structure):
+    """`aa_nl_types`: per-type-pair cutoffs of a typed neighbour list / of aa_graph_prune_*."""
+    _fields_ = [("num_types", C.c_int32), ("types_are_int64", C.c_int32), ("cutoffs", _dp), ("atom_types", C.c_void_p)]
+
+
+class PruneInput(C.Structure):
+    _fields_ = [("num_atoms", C.c_int64), ("num_edges", C.c_int64), ("pos", C.c_void_p), ("dtype", C.c_int32),
+                ("rowptr", C.c_void_p), ("nbr", C.c_void_p), ("shift_vec", C.c_void_p)]
+
+
 class AllegroLib:
     def __init__(self, cdll: C.CDLL, is_emulation: bool = False):
         self.lib = cdll
@@ -244,6 +254,22 @@ class AllegroLib:
         L.aa_nl_fill.argtypes = [C.POINTER(NlInput), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p]
         L.aa_nl_fill.restype = C.c_int
+        L.aa_nl_typed_workspace_bytes.argtypes = [C.c_int64]
+        L.aa_nl_typed_workspace_bytes.restype = C.c_size_t
+        L.aa_nl_count_typed.argtypes = [C.POINTER(NlInput), C.POINTER(NlTypes), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int64),
+                                        C.c_void_p]
+        L.aa_nl_count_typed.restype = C.c_int
+        L.aa_nl_fill_typed.argtypes = [C.POINTER(NlInput), C.POINTER(NlTypes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
+        L.aa_nl_fill_typed.restype = C.c_int
+        L.aa_graph_prune_workspace_bytes.argtypes = [C.c_int64]
+        L.aa_graph_prune_workspace_bytes.restype = C.c_size_t
+        L.aa_graph_prune_count.argtypes = [C.POINTER(PruneInput), C.POINTER(NlTypes), C.c_void_p, C.c_size_t, C.c_void_p,
+                                           C.POINTER(C.c_int64), C.c_void_p]
+        L.aa_graph_prune_count.restype = C.c_int
+        L.aa_graph_prune_fill.argtypes = [C.POINTER(PruneInput), C.POINTER(NlTypes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.aa_graph_prune_fill.restype = C.c_int
         L.aa_model_weights_bytes.argtypes = [C.c_void_p]
         L.aa_model_weights_bytes.restype = C.c_size_t
         L.aa_model_plan_layout_hash.argtypes = [C.c_void_p]

@@ -33,10 +33,34 @@ struct NlDev {
   int* scan_tmp;    // [max(cells, atoms) / 4096 + 2]
 };
 
-template <typename T>
-__global__ __launch_bounds__(256) void nl_bin_kernel(NlDev d) {
+// per-type-pair cutoffs (aa_nl_types) as the kernels see them; the untyped instantiations never touch it
+constexpr int kMaxTypes = 64;  // the squared table sits in LDS as doubles: 64 * 64 * 8 = 32 KB
+struct NlTypesDev {
+  const void* atom_types;  // [N] the caller's int32 / int64 array
+  int* wtype;              // [N] workspace: the types as int32, clamped into [0, T)
+  const double* rc2;       // [T,T] workspace: min(r_cut, table)^2
+  int* bad_type;           // workspace: set to 1 by any atom whose type was clamped
+  int T;
+};
+// the caller's type of atom i as an index into the table: never outside it, whatever the array holds
+template <typename TT>
+__device__ __forceinline__ int clamped_type(const void* atom_types, int64_t i, int T, int* bad_type) {
+  const TT t = static_cast<const TT*>(atom_types)[i];
+  if (t < 0 || t >= TT(T)) {
+    *bad_type = 1;
+    return t < 0 ? 0 : T - 1;
+  }
+  return int(t);
+}
+
+// TYPES: 0 = untyped list, 1 / 2 = the atom types (int32 / int64) are binned into the workspace next to wpos as int32, so that
+// the caller's array is read once and the pair loop reads a compact one
+template <typename T, int TYPES = 0>
+__global__ __launch_bounds__(256) void nl_bin_kernel(NlDev d, NlTypesDev ty) {
   const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
   if (i >= d.N) return;
+  if constexpr (TYPES == 1) ty.wtype[i] = clamped_type<int32_t>(ty.atom_types, i, ty.T, ty.bad_type);
+  if constexpr (TYPES == 2) ty.wtype[i] = clamped_type<int64_t>(ty.atom_types, i, ty.T, ty.bad_type);
   const T* p = static_cast<const T*>(d.pos) + 3 * i;
   const double x = double(p[0]), y = double(p[1]), z = double(p[2]);
   double s[3];
@@ -176,11 +200,22 @@ __global__ __launch_bounds__(256) void nl_cell_sort_kernel(NlDev d) {
   }
 }
 
-template <typename T, bool FILL>
+// TYPED: the cutoff of a pair is sRc2[type_i][type_j] = min(r_cut, table)^2, doubles in LDS (the table is read once per candidate
+// pair; 32 KB at the 64-type cap), instead of d.rc2.  The count (FILL = false) and the fill pass are the same code, so they apply
+// the identical predicate -- same double arithmetic, same operand order -- and rowptr always matches what fill writes.  The
+// untyped instantiation compiles to what it was before the flag existed.
+template <typename T, bool FILL, bool TYPED = false>
 __global__ __launch_bounds__(256) void nl_pairs_kernel(NlDev d, const int32_t* rowptr, int32_t* center, int32_t* nbr,
-                                                       int32_t* cell_shift, void* shift_vec) {
+                                                       int32_t* cell_shift, void* shift_vec, NlTypesDev ty) {
+  [[maybe_unused]] const double* sRow = nullptr;  // row type_i of the squared table
+  if constexpr (TYPED) {
+    double* sRc2 = reinterpret_cast<double*>(aa_smem);  // [T][T]
+    for (int q = threadIdx.x; q < ty.T * ty.T; q += 256) sRc2[q] = ty.rc2[q];
+    __syncthreads();
+  }
   const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
   if (i >= d.N) return;
+  if constexpr (TYPED) sRow = reinterpret_cast<const double*>(aa_smem) + ty.wtype[i] * ty.T;
   const double xi = d.wpos[3 * i], yi = d.wpos[3 * i + 1], zi = d.wpos[3 * i + 2];
   const int cid = d.atom_cell[i];
   const int c2 = cid % d.nc[2], c1 = (cid / d.nc[2]) % d.nc[1], c0 = cid / (d.nc[2] * d.nc[1]);
@@ -221,7 +256,12 @@ __global__ __launch_bounds__(256) void nl_pairs_kernel(NlDev d, const int32_t* r
           if (home && j == i) continue;
           const double dx = d.wpos[3 * int64_t(j)] + sx - xi, dy = d.wpos[3 * int64_t(j) + 1] + sy - yi,
                        dz = d.wpos[3 * int64_t(j) + 2] + sz - zi;
-          if (dx * dx + dy * dy + dz * dz < d.rc2) {
+          bool listed;
+          if constexpr (TYPED)
+            listed = dx * dx + dy * dy + dz * dz < sRow[ty.wtype[j]];
+          else
+            listed = dx * dx + dy * dy + dz * dz < d.rc2;
+          if (listed) {
             if constexpr (FILL) {
               center[e] = int32_t(i);
               nbr[e] = j;
@@ -255,13 +295,14 @@ size_t align_up(size_t x) { return (x + 255) / 256 * 256; }
 
 int64_t max_cells(int64_t N) { return std::max<int64_t>(64, 4 * N); }
 
-int plan_nl(const aa_nl_input* in, void* ws, size_t ws_bytes, NlDev& d) {
+// `r_list`: the radius the cell grid is sized by and d.rc2 is set from -- r_cut, or min(r_cut, largest table entry) of a typed list
+int plan_nl(const aa_nl_input* in, void* ws, size_t ws_bytes, size_t need_bytes, double r_list, NlDev& d) {
   AA_REQUIRE(in && ws, "aa_nl: null argument");
   AA_REQUIRE(in->num_atoms >= 0 && in->num_atoms < (int64_t(1) << 31), "aa_nl: atom count out of range");
   AA_REQUIRE(in->dtype == AA_F32 || in->dtype == AA_F64, "aa_nl: bad dtype");
   AA_REQUIRE(in->r_cut > 0.0, "aa_nl: r_cut must be positive");
   AA_REQUIRE(in->pos || in->num_atoms == 0, "aa_nl: null positions");
-  if (ws_bytes < aa_nl_workspace_bytes(in->num_atoms)) return fail(AA_ERR_WORKSPACE, "aa_nl: workspace too small");
+  if (ws_bytes < need_bytes) return fail(AA_ERR_WORKSPACE, "aa_nl: workspace too small");
   d.N = in->num_atoms;
   d.pos = in->pos;
   const double* c = in->cell;
@@ -284,7 +325,7 @@ int plan_nl(const aa_nl_input* in, void* ws, size_t ws_bytes, NlDev& d) {
     const double n2 = d.inv[a] * d.inv[a] + d.inv[3 + a] * d.inv[3 + a] + d.inv[6 + a] * d.inv[6 + a];
     h[a] = 1.0 / std::sqrt(n2);
     d.pbc[a] = in->pbc[a] ? 1 : 0;
-    d.nc[a] = std::max(1, int(std::min(1024.0, std::floor(h[a] / in->r_cut))));
+    d.nc[a] = std::max(1, int(std::min(1024.0, std::floor(h[a] / r_list))));
   }
   while (int64_t(d.nc[0]) * d.nc[1] * d.nc[2] > max_cells(d.N)) {  // never more cells than ~4 per atom
     int a = 0;
@@ -294,10 +335,10 @@ int plan_nl(const aa_nl_input* in, void* ws, size_t ws_bytes, NlDev& d) {
   }
   for (int a = 0; a < 3; ++a) {
     const double width = h[a] / d.nc[a];
-    d.k[a] = d.pbc[a] ? int(std::ceil(in->r_cut / width - 1e-12)) : (d.nc[a] > 1 ? 1 : 0);
+    d.k[a] = d.pbc[a] ? int(std::ceil(r_list / width - 1e-12)) : (d.nc[a] > 1 ? 1 : 0);
     AA_REQUIRE(d.k[a] <= 64, "aa_nl: cell much smaller than r_cut (more than 64 images along one direction)");
   }
-  d.rc2 = in->r_cut * in->r_cut;
+  d.rc2 = r_list * r_list;
   d.ncells = d.nc[0] * d.nc[1] * d.nc[2];
   char* base = static_cast<char*>(ws);
   size_t o = 0;
@@ -420,51 +461,363 @@ extern "C" size_t aa_nl_workspace_bytes(int64_t num_atoms) {
          align_up(sizeof(int) * (std::max(N, NC) / kScanBlock + 2));
 }
 
-extern "C" int aa_nl_count(const aa_nl_input* in, void* workspace, size_t workspace_bytes, int32_t* rowptr,
-                           int64_t* num_edges, aa_stream stream) {
+namespace {
+
+constexpr size_t kTableBytes = sizeof(double) * kMaxTypes * kMaxTypes;
+
+// what every entry point that takes an aa_nl_types checks; fills `rc2` [T*T] with min(r_cap, table)^2 (r_cap <= 0: the table alone)
+// and `r_max` with the largest of min(r_cap, table)
+int check_types(const aa_nl_types* t, int64_t num_atoms, double r_cap, const char* who, std::vector<double>& rc2, double& r_max) {
+  const std::string w(who);
+  AA_REQUIRE(t, w + ": null types");
+  AA_REQUIRE(t->num_types >= 1 && t->num_types <= kMaxTypes, w + ": num_types must lie in [1, 64]");
+  AA_REQUIRE(t->cutoffs, w + ": null cutoffs");
+  AA_REQUIRE(t->atom_types || num_atoms == 0, w + ": null atom_types");
+  const int TT = t->num_types * t->num_types;
+  rc2.resize(size_t(TT));
+  r_max = 0.0;
+  for (int q = 0; q < TT; ++q) {
+    const double c = t->cutoffs[q];
+    AA_REQUIRE(std::isfinite(c) && c > 0.0, w + ": cutoffs must be positive and finite");
+    const double r = r_cap > 0.0 ? std::min(r_cap, c) : c;
+    rc2[size_t(q)] = r * r;
+    r_max = std::max(r_max, r);
+  }
+  return AA_OK;
+}
+
+// typed workspace = the untyped one, then wtype [N], the squared table [64*64], the bad-type flag
+int plan_nl_typed(const aa_nl_input* in, const aa_nl_types* types, void* ws, size_t ws_bytes, const char* who, NlDev& d, NlTypesDev& ty,
+                  std::vector<double>& rc2) {
+  AA_REQUIRE(in, std::string(who) + ": null argument");
+  AA_REQUIRE(in->r_cut > 0.0, "aa_nl: r_cut must be positive");
+  double r_list = 0.0;
+  if (int rc = check_types(types, in->num_atoms, in->r_cut, who, rc2, r_list)) return rc;
+  if (int rc = plan_nl(in, ws, ws_bytes, aa_nl_typed_workspace_bytes(in->num_atoms), r_list, d)) return rc;
+  char* base = static_cast<char*>(ws) + aa_nl_workspace_bytes(in->num_atoms);
+  ty.atom_types = types->atom_types;
+  ty.wtype = reinterpret_cast<int*>(base);
+  base += align_up(sizeof(int) * size_t(d.N));
+  ty.rc2 = reinterpret_cast<const double*>(base);
+  base += align_up(kTableBytes);
+  ty.bad_type = reinterpret_cast<int*>(base);
+  ty.T = types->num_types;
+  return AA_OK;
+}
+
+// both list builds: `types` == nullptr is the untyped one
+int nl_count(const aa_nl_input* in, const aa_nl_types* types, void* workspace, size_t workspace_bytes, int32_t* rowptr, int64_t* num_edges,
+             aa_stream stream) {
   NlDev d{};
-  if (int rc = plan_nl(in, workspace, workspace_bytes, d)) return rc;
-  AA_REQUIRE(rowptr && num_edges, "aa_nl_count: null output");
+  NlTypesDev ty{};
+  std::vector<double> rc2;
+  const char* who = types ? "aa_nl_count_typed" : "aa_nl_count";
+  if (types) {
+    if (int rc = plan_nl_typed(in, types, workspace, workspace_bytes, who, d, ty, rc2)) return rc;
+  } else {
+    if (int rc = plan_nl(in, workspace, workspace_bytes, in ? aa_nl_workspace_bytes(in->num_atoms) : 0, in ? in->r_cut : 0.0, d)) return rc;
+  }
+  AA_REQUIRE(rowptr && num_edges, std::string(who) + ": null output");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nb = int((d.N + 255) / 256);
+  const bool f32 = in->dtype == AA_F32;
   AA_CHECK_HIP(hipMemsetAsync(d.cell_count, 0, sizeof(int) * (size_t(d.ncells) + 1), s));
+  if (types) {
+    AA_CHECK_HIP(hipMemcpyAsync(const_cast<double*>(ty.rc2), rc2.data(), sizeof(double) * rc2.size(), hipMemcpyHostToDevice, s));
+    AA_CHECK_HIP(hipMemsetAsync(ty.bad_type, 0, sizeof(int), s));
+  }
   if (d.N > 0) {
-    if (in->dtype == AA_F32)
-      hipLaunchKernelGGL(nl_bin_kernel<float>, dim3(nb), dim3(256), 0, s, d);
-    else
-      hipLaunchKernelGGL(nl_bin_kernel<double>, dim3(nb), dim3(256), 0, s, d);
+    if (!types) {
+      if (f32)
+        hipLaunchKernelGGL(nl_bin_kernel<float>, dim3(nb), dim3(256), 0, s, d, ty);
+      else
+        hipLaunchKernelGGL(nl_bin_kernel<double>, dim3(nb), dim3(256), 0, s, d, ty);
+    } else if (types->types_are_int64) {
+      if (f32)
+        hipLaunchKernelGGL((nl_bin_kernel<float, 2>), dim3(nb), dim3(256), 0, s, d, ty);
+      else
+        hipLaunchKernelGGL((nl_bin_kernel<double, 2>), dim3(nb), dim3(256), 0, s, d, ty);
+    } else {
+      if (f32)
+        hipLaunchKernelGGL((nl_bin_kernel<float, 1>), dim3(nb), dim3(256), 0, s, d, ty);
+      else
+        hipLaunchKernelGGL((nl_bin_kernel<double, 1>), dim3(nb), dim3(256), 0, s, d, ty);
+    }
   }
   launch_scan(d.cell_count, d.cell_start, int64_t(d.ncells), d.scan_tmp, s);
   if (d.N > 0) {
     hipLaunchKernelGGL(nl_cell_fill_kernel, dim3(nb), dim3(256), 0, s, d);
     hipLaunchKernelGGL(nl_cell_sort_kernel, dim3((d.ncells + 255) / 256), dim3(256), 0, s, d);
-    if (in->dtype == AA_F32)
-      hipLaunchKernelGGL((nl_pairs_kernel<float, false>), dim3(nb), dim3(256), 0, s, d, nullptr, nullptr, nullptr, nullptr, nullptr);
-    else
-      hipLaunchKernelGGL((nl_pairs_kernel<double, false>), dim3(nb), dim3(256), 0, s, d, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (types) {
+      const size_t lds = sizeof(double) * size_t(ty.T) * size_t(ty.T);
+      if (f32)
+        hipLaunchKernelGGL((nl_pairs_kernel<float, false, true>), dim3(nb), dim3(256), lds, s, d, nullptr, nullptr, nullptr, nullptr, nullptr, ty);
+      else
+        hipLaunchKernelGGL((nl_pairs_kernel<double, false, true>), dim3(nb), dim3(256), lds, s, d, nullptr, nullptr, nullptr, nullptr, nullptr, ty);
+    } else if (f32) {
+      hipLaunchKernelGGL((nl_pairs_kernel<float, false>), dim3(nb), dim3(256), 0, s, d, nullptr, nullptr, nullptr, nullptr, nullptr, ty);
+    } else {
+      hipLaunchKernelGGL((nl_pairs_kernel<double, false>), dim3(nb), dim3(256), 0, s, d, nullptr, nullptr, nullptr, nullptr, nullptr, ty);
+    }
   }
   launch_scan(d.counts, rowptr, d.N, d.scan_tmp, s);
   AA_CHECK_HIP(hipGetLastError());
-  int32_t total = 0;
+  int32_t total = 0, bad = 0;
   AA_CHECK_HIP(hipMemcpyAsync(&total, rowptr + d.N, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (types) AA_CHECK_HIP(hipMemcpyAsync(&bad, ty.bad_type, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   AA_CHECK_HIP(hipStreamSynchronize(s));
-  AA_REQUIRE(total >= 0, "aa_nl_count: more than 2^31 edges");
+  AA_REQUIRE(!bad, std::string(who) + ": atom_types outside [0, num_types)");
+  AA_REQUIRE(total >= 0, std::string(who) + ": more than 2^31 edges");
   *num_edges = total;
   return AA_OK;
 }
 
-extern "C" int aa_nl_fill(const aa_nl_input* in, void* workspace, size_t workspace_bytes, const int32_t* rowptr,
-                          int32_t* center, int32_t* nbr, int32_t* cell_shift, void* shift_vec, aa_stream stream) {
+int nl_fill(const aa_nl_input* in, const aa_nl_types* types, void* workspace, size_t workspace_bytes, const int32_t* rowptr, int32_t* center,
+            int32_t* nbr, int32_t* cell_shift, void* shift_vec, aa_stream stream) {
   NlDev d{};
-  if (int rc = plan_nl(in, workspace, workspace_bytes, d)) return rc;
-  AA_REQUIRE(rowptr && center && nbr, "aa_nl_fill: null output");
+  NlTypesDev ty{};
+  std::vector<double> rc2;
+  const char* who = types ? "aa_nl_fill_typed" : "aa_nl_fill";
+  if (types) {
+    if (int rc = plan_nl_typed(in, types, workspace, workspace_bytes, who, d, ty, rc2)) return rc;
+  } else {
+    if (int rc = plan_nl(in, workspace, workspace_bytes, in ? aa_nl_workspace_bytes(in->num_atoms) : 0, in ? in->r_cut : 0.0, d)) return rc;
+  }
+  AA_REQUIRE(rowptr && center && nbr, std::string(who) + ": null output");
   if (d.N == 0) return AA_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nb = int((d.N + 255) / 256);
-  if (in->dtype == AA_F32)
-    hipLaunchKernelGGL((nl_pairs_kernel<float, true>), dim3(nb), dim3(256), 0, s, d, rowptr, center, nbr, cell_shift, shift_vec);
-  else
-    hipLaunchKernelGGL((nl_pairs_kernel<double, true>), dim3(nb), dim3(256), 0, s, d, rowptr, center, nbr, cell_shift, shift_vec);
+  if (types) {  // (wtype and the squared table are where the count call left them)
+    const size_t lds = sizeof(double) * size_t(ty.T) * size_t(ty.T);
+    if (in->dtype == AA_F32)
+      hipLaunchKernelGGL((nl_pairs_kernel<float, true, true>), dim3(nb), dim3(256), lds, s, d, rowptr, center, nbr, cell_shift, shift_vec, ty);
+    else
+      hipLaunchKernelGGL((nl_pairs_kernel<double, true, true>), dim3(nb), dim3(256), lds, s, d, rowptr, center, nbr, cell_shift, shift_vec, ty);
+  } else if (in->dtype == AA_F32) {
+    hipLaunchKernelGGL((nl_pairs_kernel<float, true>), dim3(nb), dim3(256), 0, s, d, rowptr, center, nbr, cell_shift, shift_vec, ty);
+  } else {
+    hipLaunchKernelGGL((nl_pairs_kernel<double, true>), dim3(nb), dim3(256), 0, s, d, rowptr, center, nbr, cell_shift, shift_vec, ty);
+  }
+  AA_CHECK_HIP(hipGetLastError());
+  return AA_OK;
+}
+
+}  // namespace
+
+extern "C" size_t aa_nl_typed_workspace_bytes(int64_t num_atoms) {
+  const size_t N = size_t(std::max<int64_t>(0, num_atoms));
+  return aa_nl_workspace_bytes(num_atoms) + align_up(sizeof(int) * N) + align_up(kTableBytes) + align_up(sizeof(int));
+}
+
+extern "C" int aa_nl_count(const aa_nl_input* in, void* workspace, size_t workspace_bytes, int32_t* rowptr, int64_t* num_edges,
+                           aa_stream stream) {
+  return nl_count(in, nullptr, workspace, workspace_bytes, rowptr, num_edges, stream);
+}
+
+extern "C" int aa_nl_fill(const aa_nl_input* in, void* workspace, size_t workspace_bytes, const int32_t* rowptr, int32_t* center,
+                          int32_t* nbr, int32_t* cell_shift, void* shift_vec, aa_stream stream) {
+  return nl_fill(in, nullptr, workspace, workspace_bytes, rowptr, center, nbr, cell_shift, shift_vec, stream);
+}
+
+extern "C" int aa_nl_count_typed(const aa_nl_input* in, const aa_nl_types* types, void* workspace, size_t workspace_bytes, int32_t* rowptr,
+                                 int64_t* num_edges, aa_stream stream) {
+  AA_REQUIRE(types, "aa_nl_count_typed: null types");
+  return nl_count(in, types, workspace, workspace_bytes, rowptr, num_edges, stream);
+}
+
+extern "C" int aa_nl_fill_typed(const aa_nl_input* in, const aa_nl_types* types, void* workspace, size_t workspace_bytes,
+                                const int32_t* rowptr, int32_t* center, int32_t* nbr, int32_t* cell_shift, void* shift_vec,
+                                aa_stream stream) {
+  AA_REQUIRE(types, "aa_nl_fill_typed: null types");
+  return nl_fill(in, types, workspace, workspace_bytes, rowptr, center, nbr, cell_shift, shift_vec, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// aa_graph_prune_*: stable compaction of a center-sorted list somebody else built, by per-type-pair cutoffs.
+// ONE WAVE PER CENTER SEGMENT (four per workgroup), 64 edges per pass: the lanes read nbr / shift_vec of consecutive edges, so
+// these streams are coalesced, which a thread-per-atom loop (the form of nl_pairs_kernel, whose inner loop walks cells, not a
+// contiguous array) would not give; at the segment lengths of these lists (~10-130 edges) a wave is one to three passes per
+// center.  A surviving edge's position is out_rowptr[center] + its rank among the survivors of its segment: the rank is an
+// inclusive prefix sum over the lanes (six __shfl_up steps per pass; a ballot + popcount gives the same number -- the shuffle
+// form is the one that also runs in the CPU emulation build the tests use) plus the survivors of the earlier passes.  No atomic
+// decides a position.  Count and fill call the same prune_keeps().  The table is read from global memory (<= 32 KB, one cached
+// load per edge next to the pos[nbr] and type gathers).  Neither form was timed against the other.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct PruneDev {
+  int64_t N, E;
+  const void* pos;
+  const int32_t* rowptr;
+  const int32_t* nbr;
+  const void* shift_vec;
+  const void* atom_types;
+  const double* rc2;  // [T,T] workspace: table^2
+  int* bad_type;      // workspace
+  int* counts;        // [N+1] workspace
+  int T;
+};
+
+// (a neighbour id outside [0, N) -- a malformed list -- is dropped by both passes alike, nothing is read out of bounds)
+template <typename T, typename TT>
+__device__ __forceinline__ bool prune_keeps(const PruneDev& p, int64_t e, int j, double xi, double yi, double zi, const double* row) {
+  if (j < 0 || j >= p.N) return false;
+  const T* pj = static_cast<const T*>(p.pos) + 3 * int64_t(j);
+  double dx = double(pj[0]) - xi, dy = double(pj[1]) - yi, dz = double(pj[2]) - zi;
+  if (p.shift_vec) {
+    const T* sv = static_cast<const T*>(p.shift_vec) + 3 * e;
+    dx += double(sv[0]);
+    dy += double(sv[1]);
+    dz += double(sv[2]);
+  }
+  return dx * dx + dy * dy + dz * dz < row[clamped_type<TT>(p.atom_types, j, p.T, p.bad_type)];
+}
+
+template <typename T, typename TT, bool FILL>
+__global__ __launch_bounds__(256) void prune_kernel(PruneDev p, const int32_t* out_rowptr, int32_t* out_center, int32_t* out_nbr,
+                                                    void* out_shift_vec, int32_t* kept) {
+  const int lane = threadIdx.x & 63;
+  const int64_t a = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (a >= p.N) return;  // (wave-uniform: every lane of a wave takes part in every exchange below)
+  int64_t lo = p.rowptr[a], hi = p.rowptr[a + 1];
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > p.E ? p.E : hi;  // (row pointers beyond the list -- malformed -- read nothing)
+  if (hi <= lo) {
+    if (!FILL && lane == 0) p.counts[a] = 0;
+    return;
+  }
+  const T* pi = static_cast<const T*>(p.pos) + 3 * a;
+  const double xi = double(pi[0]), yi = double(pi[1]), zi = double(pi[2]);
+  const double* row = p.rc2 + clamped_type<TT>(p.atom_types, a, p.T, p.bad_type) * p.T;
+  int64_t o = FILL ? out_rowptr[a] : 0;  // where this pass's first survivor goes
+  int cnt = 0;
+  for (int64_t e0 = lo; e0 < hi; e0 += 64) {
+    const int64_t e = e0 + lane;
+    const int j = e < hi ? p.nbr[e] : -1;
+    const bool keep = e < hi && prune_keeps<T, TT>(p, e, j, xi, yi, zi, row);
+    if constexpr (FILL) {
+      int x = keep ? 1 : 0;
+      for (int st = 1; st < 64; st <<= 1) {
+        const int y = __shfl_up(x, st);
+        if (lane >= st) x += y;
+      }
+      if (keep) {
+        const int64_t q = o + x - 1;
+        out_center[q] = int32_t(a);
+        out_nbr[q] = j;
+        if (kept) kept[q] = int32_t(e);
+        if (out_shift_vec) {
+          T* dst = static_cast<T*>(out_shift_vec) + 3 * q;
+          if (p.shift_vec) {
+            const T* sv = static_cast<const T*>(p.shift_vec) + 3 * e;
+            dst[0] = sv[0];
+            dst[1] = sv[1];
+            dst[2] = sv[2];
+          } else {
+            dst[0] = dst[1] = dst[2] = T(0);
+          }
+        }
+      }
+      o += __shfl(x, 63);
+    } else {
+      cnt += keep ? 1 : 0;
+    }
+  }
+  if constexpr (!FILL) {
+    for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m);
+    if (lane == 0) p.counts[a] = cnt;
+  }
+}
+
+// workspace: counts [N+1], scan scratch, the squared table [64*64], the bad-type flag
+int plan_prune(const aa_prune_input* in, const aa_nl_types* types, void* ws, size_t ws_bytes, const char* who, PruneDev& p,
+               std::vector<double>& rc2, int** scan_tmp) {
+  const std::string w(who);
+  AA_REQUIRE(in && ws, w + ": null argument");
+  AA_REQUIRE(in->num_atoms >= 0 && in->num_atoms < (int64_t(1) << 31) && in->num_edges >= 0 && in->num_edges < (int64_t(1) << 31),
+             w + ": size out of range");
+  AA_REQUIRE(in->dtype == AA_F32 || in->dtype == AA_F64, w + ": bad dtype");
+  AA_REQUIRE(in->rowptr && (in->pos || in->num_atoms == 0) && (in->nbr || in->num_edges == 0), w + ": null pos, rowptr or nbr");
+  double r_max = 0.0;
+  if (int rc = check_types(types, in->num_atoms, 0.0, who, rc2, r_max)) return rc;
+  if (ws_bytes < aa_graph_prune_workspace_bytes(in->num_atoms)) return fail(AA_ERR_WORKSPACE, w + ": workspace too small");
+  const size_t N = size_t(in->num_atoms);
+  char* base = static_cast<char*>(ws);
+  p.N = in->num_atoms;
+  p.E = in->num_edges;
+  p.pos = in->pos;
+  p.rowptr = in->rowptr;
+  p.nbr = in->nbr;
+  p.shift_vec = in->shift_vec;
+  p.atom_types = types->atom_types;
+  p.T = types->num_types;
+  p.counts = reinterpret_cast<int*>(base);
+  base += align_up(sizeof(int) * (N + 1));
+  *scan_tmp = reinterpret_cast<int*>(base);
+  base += align_up(sizeof(int) * (N / kScanBlock + 2));
+  p.rc2 = reinterpret_cast<const double*>(base);
+  base += align_up(kTableBytes);
+  p.bad_type = reinterpret_cast<int*>(base);
+  return AA_OK;
+}
+
+template <bool FILL>
+void launch_prune(const PruneDev& p, int dtype, bool types64, const int32_t* out_rowptr, int32_t* out_center, int32_t* out_nbr,
+                  void* out_shift_vec, int32_t* kept, hipStream_t s) {
+  const dim3 grid((unsigned)((p.N + 3) / 4)), block(256);
+  if (dtype == AA_F32) {
+    if (types64)
+      hipLaunchKernelGGL((prune_kernel<float, int64_t, FILL>), grid, block, 0, s, p, out_rowptr, out_center, out_nbr, out_shift_vec, kept);
+    else
+      hipLaunchKernelGGL((prune_kernel<float, int32_t, FILL>), grid, block, 0, s, p, out_rowptr, out_center, out_nbr, out_shift_vec, kept);
+  } else {
+    if (types64)
+      hipLaunchKernelGGL((prune_kernel<double, int64_t, FILL>), grid, block, 0, s, p, out_rowptr, out_center, out_nbr, out_shift_vec, kept);
+    else
+      hipLaunchKernelGGL((prune_kernel<double, int32_t, FILL>), grid, block, 0, s, p, out_rowptr, out_center, out_nbr, out_shift_vec, kept);
+  }
+}
+
+}  // namespace
+
+extern "C" size_t aa_graph_prune_workspace_bytes(int64_t num_atoms) {
+  const size_t N = size_t(std::max<int64_t>(0, num_atoms));
+  return align_up(sizeof(int) * (N + 1)) + align_up(sizeof(int) * (N / kScanBlock + 2)) + align_up(kTableBytes) + align_up(sizeof(int));
+}
+
+extern "C" int aa_graph_prune_count(const aa_prune_input* in, const aa_nl_types* types, void* workspace, size_t workspace_bytes,
+                                    int32_t* out_rowptr, int64_t* out_num_edges, aa_stream stream) {
+  PruneDev p{};
+  std::vector<double> rc2;
+  int* scan_tmp = nullptr;
+  if (int rc = plan_prune(in, types, workspace, workspace_bytes, "aa_graph_prune_count", p, rc2, &scan_tmp)) return rc;
+  AA_REQUIRE(out_rowptr && out_num_edges, "aa_graph_prune_count: null output");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  AA_CHECK_HIP(hipMemcpyAsync(const_cast<double*>(p.rc2), rc2.data(), sizeof(double) * rc2.size(), hipMemcpyHostToDevice, s));
+  AA_CHECK_HIP(hipMemsetAsync(p.bad_type, 0, sizeof(int), s));
+  if (p.N > 0) launch_prune<false>(p, in->dtype, types->types_are_int64 != 0, nullptr, nullptr, nullptr, nullptr, nullptr, s);
+  launch_scan(p.counts, out_rowptr, p.N, scan_tmp, s);
+  AA_CHECK_HIP(hipGetLastError());
+  int32_t total = 0, bad = 0;
+  AA_CHECK_HIP(hipMemcpyAsync(&total, out_rowptr + p.N, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  AA_CHECK_HIP(hipMemcpyAsync(&bad, p.bad_type, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  AA_CHECK_HIP(hipStreamSynchronize(s));
+  AA_REQUIRE(!bad, "aa_graph_prune_count: atom_types outside [0, num_types)");
+  *out_num_edges = total;
+  return AA_OK;
+}
+
+extern "C" int aa_graph_prune_fill(const aa_prune_input* in, const aa_nl_types* types, void* workspace, size_t workspace_bytes,
+                                   const int32_t* out_rowptr, int32_t* out_center, int32_t* out_nbr, void* out_shift_vec, int32_t* kept,
+                                   aa_stream stream) {
+  PruneDev p{};
+  std::vector<double> rc2;
+  int* scan_tmp = nullptr;
+  if (int rc = plan_prune(in, types, workspace, workspace_bytes, "aa_graph_prune_fill", p, rc2, &scan_tmp)) return rc;
+  AA_REQUIRE(out_rowptr && out_center && out_nbr, "aa_graph_prune_fill: null output");
+  if (p.N == 0 || p.E == 0) return AA_OK;
+  // (the squared table is where the count call left it)
+  launch_prune<true>(p, in->dtype, types->types_are_int64 != 0, out_rowptr, out_center, out_nbr, out_shift_vec, kept, static_cast<hipStream_t>(stream));
   AA_CHECK_HIP(hipGetLastError());
   return AA_OK;
 }

@@ -486,11 +486,31 @@ class PreparedGraph:
                           self.atom_begin, self.atom_end, self.max_degree)
 
 
-class DeviceNeighborList:
-    """Result of `neighbor_list`: center-sorted edges on the device (`aa_nl_count` / `aa_nl_fill`)."""
+def _nl_types(atom_types: torch.Tensor, cutoffs, num_atoms: int, device, what: str):
+    """`aa_nl_types` of (atom_types, cutoffs) + what keeps its pointers alive.  The shapes are checked here; the values (table
+    entries positive and finite, at most 64 types, atom types inside the table) are checked by the library."""
+    table = torch.as_tensor(cutoffs).detach().to(device="cpu", dtype=torch.float64)
+    if table.dim() != 2 or table.shape[0] != table.shape[1]:
+        raise ValueError(f"{what}: cutoffs must be a square [T, T] table (row = center type, column = neighbour type), "
+                         f"not {list(table.shape)}")
+    if atom_types.dtype not in (torch.int32, torch.int64) or atom_types.numel() != num_atoms:
+        raise ValueError(f"{what}: atom_types must be {num_atoms} int32 or int64 values, not {list(atom_types.shape)} "
+                         f"{atom_types.dtype}")
+    if atom_types.device != device:
+        raise ValueError(f"{what}: atom_types live on {atom_types.device}, the positions on {device}")
+    table = np.ascontiguousarray(table.numpy())
+    types = atom_types.detach().reshape(-1).contiguous()
+    st = _lib.NlTypes(int(table.shape[0]), int(types.dtype == torch.int64), table.ctypes.data_as(_lib._dp), types.data_ptr())
+    return st, (table, types)
 
-    def __init__(self, edge_index, rowptr, cell_shift, shift_vec, lib=None):
+
+class DeviceNeighborList:
+    """Result of `neighbor_list`: center-sorted edges on the device (`aa_nl_count` / `aa_nl_fill`).  `kept` (lists made by
+    `prune` only): for every edge its index in the list it was pruned from."""
+
+    def __init__(self, edge_index, rowptr, cell_shift, shift_vec, lib=None, kept=None):
         self.edge_index, self.rowptr, self.cell_shift, self.shift_vec, self._lib = edge_index, rowptr, cell_shift, shift_vec, lib
+        self.kept = kept
 
     @property
     def num_edges(self) -> int:
@@ -499,6 +519,46 @@ class DeviceNeighborList:
     def prepare(self, atom_types: torch.Tensor, transposed: bool = True) -> PreparedGraph:
         return PreparedGraph(self.edge_index, atom_types, self.rowptr.numel() - 1, self.shift_vec, transposed=transposed,
                              rowptr=self.rowptr, lib=self._lib)
+
+    def prune(self, pos: torch.Tensor, atom_types: torch.Tensor, cutoffs) -> "DeviceNeighborList":
+        """The sub-list of the edges with |r_e| < cutoffs[type_center, type_neighbour] (`aa_graph_prune_*`; `cutoffs`: [T, T],
+        e.g. `model.cutoff_table()`), in the same order: what `neighbor_list(..., atom_types=, cutoffs=)` builds directly, for a
+        list that exists already.  `cell_shift` follows through `kept` [E'], the surviving edges' indices in this list.  Only
+        the new edge count crosses to the host."""
+        lib = self._lib if self._lib is not None else _lib.load()
+        _require_gpu(lib, pos, "DeviceNeighborList.prune")
+        N, E, dev = self.rowptr.numel() - 1, self.num_edges, self.edge_index.device
+        if pos.dtype not in _TORCH2AA or tuple(pos.shape) != (N, 3) or pos.device != dev:
+            raise ValueError(f"prune: pos must be [{N}, 3] float32 / float64 on {dev}, not {list(pos.shape)} {pos.dtype} on {pos.device}")
+        if self.shift_vec is not None and self.shift_vec.dtype != pos.dtype:
+            raise ValueError(f"prune: pos is {pos.dtype}, the list's shift_vec {self.shift_vec.dtype}")
+        pos = pos.detach().contiguous()
+        types, keep = _nl_types(atom_types, cutoffs, N, dev, "prune")
+        nbr = self.edge_index[1].contiguous()
+        rowptr_in = self.rowptr.contiguous()
+        sv = None if self.shift_vec is None else self.shift_vec.contiguous()
+        inp = _lib.PruneInput(N, E, pos.data_ptr(), _TORCH2AA[pos.dtype], rowptr_in.data_ptr(), nbr.data_ptr() if E else None,
+                              sv.data_ptr() if sv is not None and E else None)
+        nbytes = lib.lib.aa_graph_prune_workspace_bytes(N)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
+        n_edges = C.c_int64()
+        stream = _stream_ptr(pos)
+        with _device_ctx(dev):
+            lib.check(lib.lib.aa_graph_prune_count(C.byref(inp), C.byref(types), ws.data_ptr(), nbytes, rowptr.data_ptr(),
+                                                   C.byref(n_edges), stream), "aa_graph_prune_count")
+            E2 = int(n_edges.value)
+            edge_index = torch.empty((2, E2), dtype=torch.int32, device=dev)
+            shift_vec = None if sv is None else torch.empty((E2, 3), dtype=pos.dtype, device=dev)
+            kept = torch.empty(E2, dtype=torch.int32, device=dev)
+            if E2 > 0:
+                lib.check(lib.lib.aa_graph_prune_fill(C.byref(inp), C.byref(types), ws.data_ptr(), nbytes, rowptr.data_ptr(),
+                                                      edge_index[0].data_ptr(), edge_index[1].data_ptr(),
+                                                      shift_vec.data_ptr() if shift_vec is not None else None, kept.data_ptr(), stream),
+                          "aa_graph_prune_fill")
+        del keep
+        cell_shift = None if self.cell_shift is None else self.cell_shift.index_select(0, kept.long())
+        return DeviceNeighborList(edge_index, rowptr, cell_shift, shift_vec, lib, kept=kept)
 
     def ghost_layout(self, pos: torch.Tensor, atom_types: torch.Tensor):
         """The same list in the ghost-atom layout of the reference's `pair_allegro` contract (allegro/_compile.py:28-63),
@@ -517,10 +577,17 @@ class DeviceNeighborList:
         return pos_ext, types_ext, torch.stack((ei[0], nbr)), ghost_src
 
 
-def neighbor_list(pos: torch.Tensor, cell, pbc, r_cut: float, lib: Optional[_lib.AllegroLib] = None) -> DeviceNeighborList:
+def neighbor_list(pos: torch.Tensor, cell, pbc, r_cut: float, lib: Optional[_lib.AllegroLib] = None, *,
+                  atom_types: Optional[torch.Tensor] = None, cutoffs=None) -> DeviceNeighborList:
     """Cell-list neighbor list on the device the positions live on: every pair/image with |r| < r_cut, edges sorted by
     center (`r_e = pos[nbr] - pos[center] + cell_shift @ cell`, the `with_edge_vectors_` convention).  Only the edge
-    count crosses to the host (the outputs must be allocated).  `cell`: 3x3, lattice vectors as rows; `pbc`: 3 bools."""
+    count crosses to the host (the outputs must be allocated).  `cell`: 3x3, lattice vectors as rows; `pbc`: 3 bools.
+    With `atom_types` [N] (int32 / int64, on the device) and `cutoffs` [T, T] (row = center type, column = neighbour type;
+    `model.cutoff_table()`) an edge is listed only if |r| < min(r_cut, cutoffs[type_center, type_neighbour]): the model's
+    envelope zeroes the others anyway (`aa_nl_count_typed` / `aa_nl_fill_typed`)."""
+    if (atom_types is None) != (cutoffs is None):
+        raise ValueError("neighbor_list: atom_types and cutoffs go together (a typed list needs both; got only "
+                         f"{'atom_types' if cutoffs is None else 'cutoffs'})")
     lib = lib if lib is not None else _lib.load()
     _require_gpu(lib, pos, "neighbor_list")
     assert pos.dtype in _TORCH2AA and pos.dim() == 2 and pos.shape[1] == 3
@@ -535,18 +602,29 @@ def neighbor_list(pos: torch.Tensor, cell, pbc, r_cut: float, lib: Optional[_lib
         pbc = (pbc,) * 3
     for q in range(3):
         inp.pbc[q] = int(bool(pbc[q]))
-    nbytes = lib.lib.aa_nl_workspace_bytes(N)
+    typed = atom_types is not None
+    if typed:
+        types, keep = _nl_types(atom_types, cutoffs, N, dev, "neighbor_list")
+    nbytes = lib.lib.aa_nl_typed_workspace_bytes(N) if typed else lib.lib.aa_nl_workspace_bytes(N)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
     n_edges = C.c_int64()
     stream = _stream_ptr(pos)
-    lib.check(lib.lib.aa_nl_count(C.byref(inp), ws.data_ptr(), nbytes, rowptr.data_ptr(), C.byref(n_edges), stream),
-              "aa_nl_count")
+    if typed:
+        lib.check(lib.lib.aa_nl_count_typed(C.byref(inp), C.byref(types), ws.data_ptr(), nbytes, rowptr.data_ptr(), C.byref(n_edges),
+                                            stream), "aa_nl_count_typed")
+    else:
+        lib.check(lib.lib.aa_nl_count(C.byref(inp), ws.data_ptr(), nbytes, rowptr.data_ptr(), C.byref(n_edges), stream),
+                  "aa_nl_count")
     E = int(n_edges.value)
     edge_index = torch.empty((2, E), dtype=torch.int32, device=dev)
     cell_shift = torch.empty((E, 3), dtype=torch.int32, device=dev)
     shift_vec = torch.empty((E, 3), dtype=pos.dtype, device=dev)
-    if E > 0:
+    if E > 0 and typed:
+        lib.check(lib.lib.aa_nl_fill_typed(C.byref(inp), C.byref(types), ws.data_ptr(), nbytes, rowptr.data_ptr(),
+                                           edge_index[0].data_ptr(), edge_index[1].data_ptr(), cell_shift.data_ptr(),
+                                           shift_vec.data_ptr(), stream), "aa_nl_fill_typed")
+    elif E > 0:
         lib.check(lib.lib.aa_nl_fill(C.byref(inp), ws.data_ptr(), nbytes, rowptr.data_ptr(), edge_index[0].data_ptr(),
                                      edge_index[1].data_ptr(), cell_shift.data_ptr(), shift_vec.data_ptr(), stream),
                   "aa_nl_fill")
@@ -991,6 +1069,18 @@ class HipAllegroModel(torch.nn.Module):
         return out
 
     # -- evaluation -----------------------------------------------------------------------------
+    def cutoff_table(self) -> torch.Tensor:
+        """The per-type-pair cutoffs the model applies, [T, T] float64 on the host (row = center type, column = neighbour type):
+        1 / `edge_norm.rmax_recip`, so it follows a loaded state_dict.  What `neighbor_list(..., cutoffs=)` and
+        `DeviceNeighborList.prune` take."""
+        return 1.0 / self.func.edge_norm.rmax_recip.detach().to(device="cpu", dtype=torch.float64)
+
+    def neighbor_list(self, pos: torch.Tensor, cell, pbc, atom_types: torch.Tensor) -> DeviceNeighborList:
+        """The device neighbour list of this model: `neighbor_list` at `r_max` with the model's own `cutoff_table()`, i.e. without
+        the edges the envelope turns into exact zeros."""
+        return neighbor_list(pos, cell, pbc, self.hparams["r_max"], lib=self._bound_lib, atom_types=atom_types,
+                             cutoffs=self.cutoff_table())
+
     def prepare_graph(self, edge_index, atom_types, num_atoms, shift_vec=None) -> PreparedGraph:
         return PreparedGraph(edge_index, atom_types, num_atoms, shift_vec, lib=self._bound_lib)
 

@@ -442,6 +442,51 @@ int aa_nl_count(const aa_nl_input* in, void* workspace, size_t workspace_bytes, 
 int aa_nl_fill(const aa_nl_input* in, void* workspace, size_t workspace_bytes, const int32_t* rowptr, int32_t* center,
                int32_t* nbr, int32_t* cell_shift, void* shift_vec, aa_stream stream);
 
+/* Per-type-pair cutoffs (the model's `per_edge_type_cutoff`, nequip's EdgeLengthNormalizer): an edge i -> j is listed iff
+ *     |r_e| < min(r_cut, cutoffs[type_i * num_types + type_j])         (row = center type, column = neighbour type;
+ * the table need not be symmetric).  The envelope of the model makes every edge beyond its own pair's cutoff an exact zero, so
+ * the step computes the same numbers on the shorter list.  Errors (AA_ERR_INVALID): num_types outside [1, 64], a table entry
+ * that is not positive and finite, atom_types NULL with atoms.  An atom type outside [0, num_types) never reads outside the
+ * table: the kernels clamp it and raise a device flag, and the *_count call (which synchronises anyway) returns AA_ERR_INVALID. */
+typedef struct {
+  int32_t num_types;
+  int32_t types_are_int64; /* atom_types is int64 [N] (the pair_allegro contract) instead of int32 [N]      */
+  const double* cutoffs;   /* [num_types * num_types], HOST memory                                        */
+  const void* atom_types;  /* [N], device memory                                                          */
+} aa_nl_types;
+/* aa_nl_count / aa_nl_fill with the predicate above: same two phases, same outputs, same edge order as the untyped list at
+ * min(r_cut, largest table entry) with the dropped edges removed (the cell grid is sized by that radius); a table whose entries
+ * all reach r_cut gives the untyped list bit for bit.  `workspace`: aa_nl_typed_workspace_bytes(num_atoms). */
+size_t aa_nl_typed_workspace_bytes(int64_t num_atoms);
+int aa_nl_count_typed(const aa_nl_input* in, const aa_nl_types* types, void* workspace, size_t workspace_bytes, int32_t* rowptr,
+                      int64_t* num_edges, aa_stream stream);
+int aa_nl_fill_typed(const aa_nl_input* in, const aa_nl_types* types, void* workspace, size_t workspace_bytes,
+                     const int32_t* rowptr, int32_t* center, int32_t* nbr, int32_t* cell_shift, void* shift_vec, aa_stream stream);
+
+/* The same reduction for a center-sorted list somebody else built at the largest cutoff (a LAMMPS list, an untyped aa_nl list):
+ * stable compaction, keeping edge e iff |pos[nbr_e] - pos[center_e] + shift_vec_e| < cutoffs[type_center][type_nbr] (evaluated in
+ * double; shift_vec NULL = no shifts, the ghost-atom layout).  Output order is input order; every position comes from a prefix
+ * sum, none from an atomic: bit-reproducible.  Two phases like aa_nl_*:
+ *   aa_graph_prune_count  writes out_rowptr [N+1] (device) and returns E' (synchronises the stream);
+ *   aa_graph_prune_fill   writes out_center / out_nbr [E'] and, where not NULL, out_shift_vec [E',3] (`dtype`) and kept [E'] =
+ *                         the input edge id of every surviving edge (to carry cell shifts or anything else along).
+ * Same arguments and the same `workspace` (aa_graph_prune_workspace_bytes(num_atoms) bytes of device scratch) for both calls.
+ * The outputs must not alias the inputs.  Run aa_graph_transpose on the result. */
+typedef struct {
+  int64_t num_atoms, num_edges;
+  const void* pos;         /* [N,3] device, `dtype`                                            */
+  int32_t dtype;           /* aa_dtype of pos / shift_vec                                      */
+  const int32_t* rowptr;   /* [N+1] device                                                     */
+  const int32_t* nbr;      /* [E] device                                                       */
+  const void* shift_vec;   /* [E,3] device, `dtype`, or NULL                                   */
+} aa_prune_input;
+size_t aa_graph_prune_workspace_bytes(int64_t num_atoms);
+int aa_graph_prune_count(const aa_prune_input* in, const aa_nl_types* types, void* workspace, size_t workspace_bytes,
+                         int32_t* out_rowptr, int64_t* out_num_edges, aa_stream stream);
+int aa_graph_prune_fill(const aa_prune_input* in, const aa_nl_types* types, void* workspace, size_t workspace_bytes,
+                        const int32_t* out_rowptr, int32_t* out_center, int32_t* out_nbr, void* out_shift_vec, int32_t* kept,
+                        aa_stream stream);
+
 /* Transposed CSR of a center-sorted edge list on the device -- `t_rowptr` [N+1], `t_perm` [E]: edge ids grouped by NEIGHBOUR atom in
  * ascending order (= the stable argsort of `nbr`), what aa_graph.t_rowptr / t_perm ask for so that forces are gathered per atom in a
  * fixed order -- and, with `hints3` != NULL (device int32[3]; needs `rowptr`), the three graph hints {atom_begin, atom_end,
