@@ -78,7 +78,13 @@ extern "C" void aa_tp_plan_destroy(aa_tp_plan* plan) {
 extern "C" int aa_tp_forward(const aa_tp_plan* plan, int64_t E, int64_t N, const void* x1, const void* x2,
                              const void* weights, const int32_t* rowptr, const int32_t* eids, double scatter_factor,
                              void* x2s, void* out, aa_stream stream) {
-  AA_REQUIRE(plan && x1 && x2 && weights && rowptr && x2s && out, "aa_tp_forward: null argument");
+  AA_REQUIRE(plan && weights && rowptr && (N == 0 || x2s), "aa_tp_forward: null argument");
+  AA_REQUIRE(E == 0 || (x1 && x2 && out), "aa_tp_forward: null edge tensor");
+  if (E == 0) {  // a frame or shard without edges: no rows of x1 / x2 / out; the scatter-sum of nothing is zero
+    const size_t row = size_t(plan->dev.mul) * plan->dev.d2 * (plan->dtype == AA_F32 ? 4 : 8);
+    if (N > 0) AA_CHECK_HIP(hipMemsetAsync(x2s, 0, size_t(N) * row, static_cast<hipStream_t>(stream)));
+    return AA_OK;
+  }
   if (plan->dense_spec) {
     TpDenseArgs d{};
     d.E = E;
@@ -114,7 +120,9 @@ extern "C" int aa_tp_forward(const aa_tp_plan* plan, int64_t E, int64_t N, const
 extern "C" int aa_tp_backward(const aa_tp_plan* plan, int64_t E, int64_t N, const void* x1, const void* x2s,
                               const void* weights, const int32_t* rowptr, const int32_t* eids, double scatter_factor,
                               const void* gout, void* gx1, void* gx2, aa_stream stream) {
-  AA_REQUIRE(plan && weights && rowptr && gout && (gx1 || gx2), "aa_tp_backward: null argument");
+  AA_REQUIRE(plan && weights && rowptr, "aa_tp_backward: null argument");
+  if (E == 0) return AA_OK;  // no edges: gx1 / gx2 have no rows, nothing is read or written
+  AA_REQUIRE(gout && (gx1 || gx2), "aa_tp_backward: null argument");
   AA_REQUIRE((!gx1 || x2s) && (!gx2 || x1), "aa_tp_backward: a requested gradient's operand is null");
   if (plan->dense_spec) {
     TpDenseArgs d{};

@@ -77,7 +77,9 @@ int aa_tp_plan_is_specialised(const aa_tp_plan* plan); /* 1: aa_tp_forward / aa_
  *   out[e] = contract(x1[e], x2s[center(e)])                                  (:205-211)
  * eids (nullable): sorted position -> edge id, for callers whose `idxs` are not sorted
  * (tests/nn/test_contract_kernels.py:95-97).  x1:[E,u,d1] x2:[E,u,d2] out:[E,u,dout],
- * weights: [u,p] or [p] (device), x2s: [N,u,d2] caller buffer (kept for the backward). */
+ * weights: [u,p] or [p] (device), x2s: [N,u,d2] caller buffer (kept for the backward).
+ * E == 0 (a frame or shard without edges): x1, x2 and out have no rows and may be NULL; x2s is set to zero (N > 0);
+ * N == 0: x2s may be NULL too, nothing is written. */
 int aa_tp_forward(const aa_tp_plan* plan, int64_t E, int64_t N, const void* x1, const void* x2,
                   const void* weights, const int32_t* rowptr, const int32_t* eids,
                   double scatter_factor, void* x2s, void* out, aa_stream stream);
@@ -85,7 +87,8 @@ int aa_tp_forward(const aa_tp_plan* plan, int64_t E, int64_t N, const void* x1, 
 /* input gradients of the above: gx1:[E,u,d1], gx2:[E,u,d2].  Either output may be NULL: that gradient is not computed and
  * the operand only it reads may be NULL too (gx1 == NULL: x2s unused; gx2 == NULL: x1 unused) -- the single partial
  * contractions the training path differentiates through (allegro_amd/ops.py; the reference gets them from autograd
- * through the eager contraction, _contract.py:213-251). */
+ * through the eager contraction, _contract.py:213-251).
+ * E == 0: the edge tensors (x1, gout, gx1, gx2) have no rows and may all be NULL; AA_OK, nothing is read or written. */
 int aa_tp_backward(const aa_tp_plan* plan, int64_t E, int64_t N, const void* x1, const void* x2s,
                    const void* weights, const int32_t* rowptr, const int32_t* eids,
                    double scatter_factor, const void* gout, void* gx1, void* gx2, aa_stream stream);
