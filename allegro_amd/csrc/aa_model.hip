@@ -212,7 +212,7 @@ enum class TpPath {
 };
 enum class LinearPath {
   Single,  // one launch per linear layer
-  Slot,    // single layers on output-folded weights, reverse by dense-net slot (aa_model_plan::s_*)
+  Slot,    // single layers on output-folded weights, reverse by dense-net slot (BlobLayout::s_*)
   Chains,  // MLP chains fused into gemm_chain_bf16x3_kernel (hidden layers stay in registers)
 };
 
@@ -536,33 +536,31 @@ struct GemmMatSet {
   int K = 0, N = 0, count = 0;
 };
 
-struct aa_model_plan {
-  aa_model_config cfg;               // at the widened sizes of `pipe`
-  aa_plan_options opt{};
-  ModelPipeline pipe{};              // what the plan runs: set by choose_pipeline in aa_model_plan_create, read everywhere else
-  int D, R, W, SL1;  // SH dim, irreps, env weight numel, S*(L+1)
-  std::vector<std::vector<int32_t>> keep_i32;
-  std::vector<std::vector<double>> keep_f64;
-  std::vector<TpLayerDev> layers;
-  std::vector<void*> owned;
-  // weight blob layout (element offsets)
-  size_t o_rmax, o_bessel, o_cemb, o_nemb, o_basis, o_g0, o_g0t, o_g0p, o_g0tp, o_g0q, o_g0tq, o_b3a_q, o_b3b_q, o_b3c_q, o_ro_last, o_scales, o_shifts, n_elems;
-  size_t o_tpw[AA_MAX_LAYERS];
+static std::vector<int> mlp_dims(int in, int depth, int width, int out) {
+  std::vector<int> d{in};
+  for (int i = 0; i < depth; ++i) d.push_back(width);
+  d.push_back(out);
+  return d;
+}
+
+// Where every entry of the packed weight blob lies (element offsets) and what shape it has.  layout_blob is the only writer: the
+// plan keeps the value, and the packer, the Runner, layout_workspace and the debug taps read it.
+struct BlobLayout {
+  size_t o_rmax = 0, o_bessel = 0, o_cemb = 0, o_nemb = 0, o_basis = 0, o_g0 = 0, o_g0t = 0, o_g0p = 0, o_g0tp = 0, o_g0q = 0, o_g0tq = 0,
+         o_b3a_q = 0, o_b3b_q = 0, o_b3c_q = 0, o_ro_last = 0, o_scales = 0, o_shifts = 0, n_elems = 0;
+  size_t o_tpw[AA_MAX_LAYERS] = {};
   MlpLayout embed, readout;          // readout: only the GEMM layers (all but the final ->1 layer)
   MlpLayout latent[AA_MAX_LAYERS];
-  int ro_last_dim;                   // input dim of the final readout linear
-  int u_raw;                         // num_tensor_features of the model; cfg.num_tensor is the next multiple of 64 when the channels were padded
-  int hid_raw[3];                    // hidden widths of scalar_embed_mlp / latent MLPs / edge_readout in the model (cfg holds the padded ones)
-  mutable bool taps = false;         // aa_model_plan_enable_taps: staged pipeline so that every tap is materialised
-  // blob offsets of the optional parts: positions only, 0 where the part is absent -- whether it exists is pipe's to say
-  size_t o_embtab;                   // (two_body_table) [T*T][8][64] type_embed(c | pair) * basis_linear[n][c]
-  size_t o_embtab_h;                 // (fold_embed_table) [T*T][8][64] the same table times the first scalar_embed_mlp layer
-  size_t o_lat1in_fq, o_ro0_fq;      // (fold_latent_outputs, 2-layer 64-wide stacks) bf16x3 copies of the first layers of latent 1 / edge_readout with the
+  int ro_last_dim = 0;               // input dim of the final readout linear
+  // the optional parts: positions only, 0 where the part is absent -- whether it exists is the pipeline's to say
+  size_t o_embtab = 0;               // (two_body_table) [T*T][8][64] type_embed(c | pair) * basis_linear[n][c]
+  size_t o_embtab_h = 0;             // (fold_embed_table) [T*T][8][64] the same table times the first scalar_embed_mlp layer
+  size_t o_lat1in_fq = 0, o_ro0_fq = 0;  // (fold_latent_outputs, 2-layer 64-wide stacks) bf16x3 copies of the first layers of latent 1 / edge_readout with the
                                      // latent output layers folded into their lat_l row blocks
-  size_t o_b3af_q;                   // ... and of the merged first layer of the readout-reverse chain
-  size_t o_b3bf_q;                   // (fold_lat0_reverse) ... and of its second layer with Wout_0^T folded into the lat0 columns (d a_0 instead of d lat0)
-  size_t o_g0fq, o_g0tfq;            // (fold_embed_output) bf16x3 copies of W1 @ G0 [64, ng0] and of its transpose
-  size_t o_wk0f, o_wt0f;             // (fold_embed_output) W1 @ Wenv0 as [k][R][u] and [R][u][k]
+  size_t o_b3af_q = 0;               // ... and of the merged first layer of the readout-reverse chain
+  size_t o_b3bf_q = 0;               // (fold_lat0_reverse) ... and of its second layer with Wout_0^T folded into the lat0 columns (d a_0 instead of d lat0)
+  size_t o_g0fq = 0, o_g0tfq = 0;    // (fold_embed_output) bf16x3 copies of W1 @ G0 [64, ng0] and of its transpose
+  size_t o_wk0f = 0, o_wt0f = 0;     // (fold_embed_output) W1 @ Wenv0 as [k][R][u] and [R][u][k]
   // "Slot form" of the single-layer pipeline (LinearPath::Slot; operator-kernel plans: C5 and every standard stack off the tuned 2-layer shape).
   // The same algebra as fold_embed_output / fold_latent_outputs (aa_common.h), for any depth: the output layer of scalar_embed_mlp and of every latent MLP is
   // folded into its consumers at pack time, so slot l + 1 of the dense-net buffer holds the latent's hidden PRE-ACTIVATION z_l
@@ -576,12 +574,192 @@ struct aa_model_plan {
   GemmMat s_rs[AA_MAX_LAYERS];       //   reverse stack of slot l + 1: rows [readout | latent l+1 .. L-1] -> d a_l  [Hr + S (L-1-l), H]
   GemmMat s_rstb;                    //   reverse stack of slot 0 (two-body): rows [readout | latent 0 .. L-1]      [Hr + S L, S]
   GemmMat s_sct[AA_MAX_LAYERS];      //   d z_l -> d (tensor scalars of layer l)                                   [H, u]
-  size_t o_s_wk0, o_s_wt0;           //   W_last(embed) @ Wenv0 as [k][R][u] and [R][u][k]
+  size_t o_s_wk0 = 0, o_s_wt0 = 0;   //   W_last(embed) @ Wenv0 as [k][R][u] and [R][u][k]
   // operator-kernel plans (pipe.op_proj): the env projections as batched linear-layer launches (TpOpArgs::proj_gemm) -- per layer the R matrices
   // f Wenv_l[:, r, :] [ka, u] and their transposes [u, ka]; layer 0 also behind the output layer of scalar_embed_mlp (slot form)
   GemmMatSet s_pr[AA_MAX_LAYERS], s_prt[AA_MAX_LAYERS], s_pr0f, s_prt0f;
-  int ng0;                           // output width of the fused first-stage GEMM
-  size_t o_wk[AA_MAX_LAYERS], o_wt[AA_MAX_LAYERS];  // Wenv of layer l as [ka][R][u] and [R][u][ka]
+  int ng0 = 0;                       // output width of the fused first-stage GEMM
+  size_t o_wk[AA_MAX_LAYERS] = {}, o_wt[AA_MAX_LAYERS] = {};  // (moments / operator plans) Wenv of layer l as [ka][R][u] and [R][u][ka]
+
+  uint64_t hash(const aa_model_config& c, const ModelPipeline& pipe, int u_raw) const;
+};
+
+// The blob layout of a pipeline, from the widened configuration and the pipeline alone: no HIP call, nothing read from a plan.
+// THE ORDER OF THE take() CALLS IS THE BLOB FORMAT: every entry starts on a multiple of 64 elements, in the order taken.
+static BlobLayout layout_blob(const aa_model_config& c, const ModelPipeline& pipe) {
+  BlobLayout b;
+  const int L = c.num_layers, S = c.num_scalar, u = c.num_tensor, T = c.num_types, B = c.num_bessels, S0 = c.embed_dim;
+  const int R = c.l_max + 1, W = R * u, SL1 = S * (L + 1), Hr = c.readout_mlp_width, H = c.latent_mlp_width;
+  size_t o = 0;
+  auto take = [&](size_t n) {
+    size_t r = o;
+    o += (n + 63) / 64 * 64;
+    return r;
+  };
+  auto lay = [&](MlpLayout& m, const std::vector<int>& dims, int nlayers) {
+    m.dims = dims;
+    for (int i = 0; i < nlayers; ++i) {
+      m.w.push_back(take(size_t(dims[i]) * dims[i + 1]));
+      m.wt.push_back(take(size_t(dims[i]) * dims[i + 1]));
+      m.wp.push_back(take(gemm_packed_elems(dims[i], dims[i + 1])));
+      m.wtp.push_back(take(gemm_packed_elems(dims[i + 1], dims[i])));
+      m.wq.push_back(take(gemm_bf16x3_words(dims[i], dims[i + 1])));
+      m.wtq.push_back(take(gemm_bf16x3_words(dims[i + 1], dims[i])));
+    }
+  };
+  // (braced initialisers are evaluated left to right: w, wp, wq are taken in this order)
+  auto mat = [&](int K, int N) { return GemmMat{take(size_t(K) * N), take(gemm_packed_elems(K, N)), take(gemm_bf16x3_words(K, N)), K, N}; };
+  auto mset = [&](int K, int N, int count) {
+    auto r64 = [](size_t n) { return (n + 63) / 64 * 64; };
+    const size_t w_bs = r64(size_t(K) * N), wp_bs = r64(gemm_packed_elems(K, N)), wq_bs = r64(gemm_bf16x3_words(K, N));
+    return GemmMatSet{take(w_bs * count), take(wp_bs * count), take(wq_bs * count), w_bs, wp_bs, wq_bs, K, N, count};
+  };
+  b.o_rmax = take(size_t(T) * T);
+  b.o_bessel = take(B);
+  b.o_cemb = take(size_t(T) * S0 / 2);
+  b.o_nemb = take(size_t(T) * S0 / 2);
+  b.o_basis = take(size_t(B) * S0);
+  lay(b.embed, mlp_dims(S0, c.embed_mlp_depth, c.embed_mlp_width, S), c.embed_mlp_depth + 1);
+  b.ng0 = pipe.env_moments() ? S + W : S + 2 * W;
+  b.o_g0 = take(size_t(S) * b.ng0);
+  b.o_g0t = take(size_t(S) * b.ng0);
+  b.o_g0p = take(gemm_packed_elems(S, b.ng0));
+  b.o_g0tp = take(gemm_packed_elems(b.ng0, S));
+  b.o_g0q = take(gemm_bf16x3_words(S, b.ng0));
+  b.o_g0tq = take(gemm_bf16x3_words(b.ng0, S));
+  if (pipe.env_moments()) {
+    for (int l = 0; l < L; ++l) {
+      const size_t ka = l == 0 ? S : H;
+      b.o_wk[l] = take(ka * W);
+      b.o_wt[l] = take(ka * W);
+    }
+  }
+  for (int l = 0; l < L; ++l) {
+    int in = S * (l + 1) + u, outd = S + ((l < L - 1 && !pipe.env_moments()) ? W : 0);
+    lay(b.latent[l], mlp_dims(in, c.latent_mlp_depth, H, outd), c.latent_mlp_depth + 1);
+    b.o_tpw[l] = take(size_t(c.tps[l].coupling ? u : 1) * c.tps[l].num_paths);
+  }
+  {
+    std::vector<int> rd = mlp_dims(SL1, c.readout_mlp_depth, Hr, 1);
+    lay(b.readout, rd, c.readout_mlp_depth);  // all but the last layer
+    b.ro_last_dim = rd[rd.size() - 2];
+    b.o_ro_last = take(b.ro_last_dim);
+  }
+  if (pipe.fold_embed_output) {
+    b.o_g0fq = take(gemm_bf16x3_words(64, b.ng0));
+    b.o_g0tfq = take(gemm_bf16x3_words(b.ng0, 64));
+    b.o_wk0f = take(size_t(64) * W);
+    b.o_wt0f = take(size_t(64) * W);
+  }
+  if (pipe.fold_latent_outputs) {  // (S = u = every MLP width = 64, one hidden layer each, L = 2)
+    b.o_lat1in_fq = take(gemm_bf16x3_words(2 * S + u, 64));
+    b.o_ro0_fq = take(gemm_bf16x3_words(3 * S, 64));
+    b.o_b3af_q = take(gemm_bf16x3_words(64, 64));
+    b.o_b3bf_q = pipe.fold_lat0_reverse ? take(gemm_bf16x3_words(128, S * L)) : 0;
+  }
+  b.o_embtab = pipe.two_body_table ? take(size_t(T) * T * B * S0) : 0;
+  b.o_embtab_h = pipe.fold_embed_table ? take(size_t(T) * T * B * 64) : 0;
+  if (pipe.chains()) {
+    // merged reverse chain "readout' o latent_{L-1}'" (see Runner::backward): the readout-reverse columns that feed
+    // the last latent, and [readout-reverse columns of the earlier features (zero-padded) ; latent-reverse] stacked
+    b.o_b3a_q = take(gemm_bf16x3_words(64, S));
+    b.o_b3b_q = take(gemm_bf16x3_words(128, S * L));
+    b.o_b3c_q = take(gemm_bf16x3_words(64, u));
+  }
+  if (pipe.slot()) {
+    b.s_g0f = mat(S, b.ng0);
+    b.s_g0ft = mat(b.ng0, S);
+    for (int l = 0; l < L; ++l) {
+      b.s_in[l] = mat(S * (l + 1) + u, H);
+      b.s_rs[l] = mat(Hr + S * (L - 1 - l), H);
+      b.s_sct[l] = mat(H, u);
+    }
+    b.s_ro0 = mat(SL1, Hr);
+    b.s_rstb = mat(Hr + S * L, S);
+    b.o_s_wk0 = take(size_t(S) * W);
+    b.o_s_wt0 = take(size_t(S) * W);
+  }
+  if (pipe.op_proj) {
+    for (int l = 0; l < L; ++l) {
+      const int ka = l == 0 ? S : H;
+      b.s_pr[l] = mset(ka, u, R);
+      b.s_prt[l] = mset(u, ka, R);
+    }
+    if (pipe.slot()) {
+      b.s_pr0f = mset(S, u, R);
+      b.s_prt0f = mset(u, S, R);
+    }
+  }
+  b.o_scales = take(T);
+  b.o_shifts = take(T);
+  b.n_elems = o;
+  return b;
+}
+
+// FNV-1a over every quantity the blob is laid out by (aa_model_plan_layout_hash: exported packages and host model files carry
+// the value, so neither the quantities nor their order may change).  The lists below are kept by hand, and still no new entry
+// can go unnoticed: n_elems and the offset of every later entry -- o_scales and o_shifts at least -- move when one is added.
+uint64_t BlobLayout::hash(const aa_model_config& c, const ModelPipeline& pipe, int u_raw) const {
+  uint64_t h = 1469598103934665603ull;
+  auto mix = [&](uint64_t v) {
+    for (int i = 0; i < 8; ++i) {
+      h ^= (v >> (8 * i)) & 0xff;
+      h *= 1099511628211ull;
+    }
+  };
+  auto mixv = [&](const std::vector<size_t>& v) {
+    mix(v.size());
+    for (size_t x : v) mix(x);
+  };
+  auto mixm = [&](const MlpLayout& m) {
+    mix(m.dims.size());
+    for (int d : m.dims) mix(uint64_t(d));
+    mixv(m.w); mixv(m.wt); mixv(m.wp); mixv(m.wtp); mixv(m.wq); mixv(m.wtq);
+  };
+  for (uint64_t v : {uint64_t(c.dtype), uint64_t(c.num_types), uint64_t(c.num_bessels), uint64_t(c.l_max), uint64_t(c.num_layers),
+                     uint64_t(c.num_scalar), uint64_t(c.num_tensor), uint64_t(c.embed_dim), uint64_t(c.embed_mlp_width),
+                     uint64_t(c.latent_mlp_width), uint64_t(c.readout_mlp_width), uint64_t(u_raw), uint64_t(pipe.channel_minor()),
+                     uint64_t(pipe.env_moments()), uint64_t(pipe.chains()), uint64_t(pipe.chain_pair + 1), uint64_t(pipe.tp_op + 1), uint64_t(ng0),
+                     uint64_t(n_elems), uint64_t(pipe.slot())})
+    mix(v);
+  if (pipe.slot()) {
+    auto mixg = [&](const GemmMat& m) { mix(m.w); mix(m.wp); mix(m.wq); };
+    mixg(s_g0f); mixg(s_g0ft); mixg(s_ro0); mixg(s_rstb);
+    for (int l = 0; l < c.num_layers; ++l) { mixg(s_in[l]); mixg(s_rs[l]); mixg(s_sct[l]); }
+    mix(o_s_wk0); mix(o_s_wt0);
+  }
+  if (pipe.op_proj) {
+    auto mixs = [&](const GemmMatSet& m) { mix(m.w); mix(m.wp); mix(m.wq); mix(m.w_bs); };
+    for (int l = 0; l < c.num_layers; ++l) { mixs(s_pr[l]); mixs(s_prt[l]); }
+    mixs(s_pr0f); mixs(s_prt0f);
+  }
+  for (size_t v : {o_rmax, o_bessel, o_cemb, o_nemb, o_basis, o_g0, o_g0t, o_g0p, o_g0tp, o_g0q, o_g0tq,
+                   o_b3a_q, o_b3b_q, o_b3c_q, o_ro_last, o_scales, o_shifts, o_embtab, o_embtab_h, o_lat1in_fq, o_ro0_fq, o_b3af_q, o_b3bf_q, o_g0fq, o_g0tfq, o_wk0f, o_wt0f})
+    mix(v);
+  for (int l = 0; l < c.num_layers; ++l) {
+    mix(o_tpw[l]);
+    mix(o_wk[l]);
+    mix(o_wt[l]);
+    mixm(latent[l]);
+  }
+  mixm(embed);
+  mixm(readout);
+  return h ? h : 1;
+}
+
+struct aa_model_plan {
+  aa_model_config cfg;               // at the widened sizes of `pipe`
+  aa_plan_options opt{};
+  ModelPipeline pipe{};              // what the plan runs: set by choose_pipeline in aa_model_plan_create, read everywhere else
+  int D, R, W, SL1;  // SH dim, irreps, env weight numel, S*(L+1)
+  std::vector<std::vector<int32_t>> keep_i32;
+  std::vector<std::vector<double>> keep_f64;
+  std::vector<TpLayerDev> layers;
+  std::vector<void*> owned;
+  BlobLayout blob;                   // where each weight lies in the packed blob: set once by layout_blob in aa_model_plan_create, read everywhere else
+  int u_raw;                         // num_tensor_features of the model; cfg.num_tensor is the next multiple of 64 when the channels were padded
+  int hid_raw[3];                    // hidden widths of scalar_embed_mlp / latent MLPs / edge_readout in the model (cfg holds the padded ones)
+  mutable bool taps = false;         // aa_model_plan_enable_taps: staged pipeline so that every tap is materialised
   size_t esize() const { return cfg.dtype == AA_F32 ? 4 : 8; }
   // optional hipGraph replay of the whole step (aa_model_plan_enable_graph): the launch sequence is captured once per
   // distinct argument set and replayed with one hipGraphLaunch -- for launch-bound (small) systems
@@ -630,13 +808,6 @@ static int consume_status(const aa_model_plan* plan, const char* who) {
   return fail(AA_ERR_INVALID, msg);
 }
 
-static std::vector<int> mlp_dims(int in, int depth, int width, int out) {
-  std::vector<int> d{in};
-  for (int i = 0; i < depth; ++i) d.push_back(width);
-  d.push_back(out);
-  return d;
-}
-
 static int validate_config(const aa_model_config* cfg) {
   AA_REQUIRE(cfg->dtype == AA_F32 || cfg->dtype == AA_F64, "model: bad dtype");
   AA_REQUIRE(cfg->l_max >= 1 && cfg->l_max <= 3, "model: l_max must be 1..3");
@@ -656,7 +827,7 @@ extern "C" int aa_model_plan_create(const aa_model_config* cfg, aa_model_plan** 
   return aa_model_plan_create_with_options(cfg, nullptr, out);
 }
 
-// validate -> choose_pipeline -> lay out the weight blob
+// validate -> choose_pipeline -> widen the configuration -> build the tensor-product layers -> layout_blob -> status word
 extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, const aa_plan_options* options, aa_model_plan** out) {
   AA_REQUIRE(cfg_in && out, "aa_model_plan_create: null argument");
   if (int rc = validate_config(cfg_in)) return rc;
@@ -698,134 +869,7 @@ extern "C" int aa_model_plan_create_with_options(const aa_model_config* cfg_in, 
     p->cfg.tps[l].nz_i = p->cfg.tps[l].nz_j = p->cfg.tps[l].nz_k = p->cfg.tps[l].nz_path = nullptr;
     p->cfg.tps[l].nz_val = nullptr;
   }
-  // weight blob layout
-  size_t o = 0;
-  auto take = [&](size_t n) {
-    size_t r = o;
-    o += (n + 63) / 64 * 64;
-    return r;
-  };
-  const int T = cfg->num_types, B = cfg->num_bessels, S0 = cfg->embed_dim;
-  p->o_rmax = take(size_t(T) * T);
-  p->o_bessel = take(B);
-  p->o_cemb = take(size_t(T) * S0 / 2);
-  p->o_nemb = take(size_t(T) * S0 / 2);
-  p->o_basis = take(size_t(B) * S0);
-  auto lay = [&](MlpLayout& m, const std::vector<int>& dims, int nlayers) {
-    m.dims = dims;
-    for (int i = 0; i < nlayers; ++i) {
-      m.w.push_back(take(size_t(dims[i]) * dims[i + 1]));
-      m.wt.push_back(take(size_t(dims[i]) * dims[i + 1]));
-      m.wp.push_back(take(gemm_packed_elems(dims[i], dims[i + 1])));
-      m.wtp.push_back(take(gemm_packed_elems(dims[i + 1], dims[i])));
-      m.wq.push_back(take(gemm_bf16x3_words(dims[i], dims[i + 1])));
-      m.wtq.push_back(take(gemm_bf16x3_words(dims[i + 1], dims[i])));
-    }
-  };
-  lay(p->embed, mlp_dims(S0, cfg->embed_mlp_depth, cfg->embed_mlp_width, S), cfg->embed_mlp_depth + 1);
-  p->ng0 = pipe.env_moments() ? S + p->W : S + 2 * p->W;
-  p->o_g0 = take(size_t(S) * p->ng0);
-  p->o_g0t = take(size_t(S) * p->ng0);
-  p->o_g0p = take(gemm_packed_elems(S, p->ng0));
-  p->o_g0tp = take(gemm_packed_elems(p->ng0, S));
-  p->o_g0q = take(gemm_bf16x3_words(S, p->ng0));
-  p->o_g0tq = take(gemm_bf16x3_words(p->ng0, S));
-  if (pipe.env_moments()) {
-    for (int l = 0; l < L; ++l) {
-      const size_t ka = l == 0 ? S : cfg->latent_mlp_width;
-      p->o_wk[l] = take(ka * p->W);
-      p->o_wt[l] = take(ka * p->W);
-    }
-  }
-  for (int l = 0; l < L; ++l) {
-    int in = S * (l + 1) + u, outd = S + ((l < L - 1 && !pipe.env_moments()) ? p->W : 0);
-    lay(p->latent[l], mlp_dims(in, cfg->latent_mlp_depth, cfg->latent_mlp_width, outd), cfg->latent_mlp_depth + 1);
-    p->o_tpw[l] = take(size_t(cfg->tps[l].coupling ? u : 1) * cfg->tps[l].num_paths);
-  }
-  {
-    std::vector<int> rd = mlp_dims(p->SL1, cfg->readout_mlp_depth, cfg->readout_mlp_width, 1);
-    lay(p->readout, rd, cfg->readout_mlp_depth);  // all but the last layer
-    p->ro_last_dim = rd[rd.size() - 2];
-    p->o_ro_last = take(p->ro_last_dim);
-  }
-  p->o_b3a_q = p->o_b3b_q = p->o_b3c_q = 0;
-  p->o_lat1in_fq = p->o_ro0_fq = p->o_b3af_q = p->o_b3bf_q = 0;
-  p->o_g0fq = p->o_g0tfq = p->o_wk0f = p->o_wt0f = 0;
-  if (pipe.fold_embed_output) {
-    p->o_g0fq = take(gemm_bf16x3_words(64, p->ng0));
-    p->o_g0tfq = take(gemm_bf16x3_words(p->ng0, 64));
-    p->o_wk0f = take(size_t(64) * p->W);
-    p->o_wt0f = take(size_t(64) * p->W);
-  }
-  if (pipe.fold_latent_outputs) {  // (S = u = every MLP width = 64, one hidden layer each, L = 2)
-    p->o_lat1in_fq = take(gemm_bf16x3_words(2 * S + u, 64));
-    p->o_ro0_fq = take(gemm_bf16x3_words(3 * S, 64));
-    p->o_b3af_q = take(gemm_bf16x3_words(64, 64));
-    p->o_b3bf_q = pipe.fold_lat0_reverse ? take(gemm_bf16x3_words(128, S * L)) : 0;
-  }
-  p->o_embtab = pipe.two_body_table ? take(size_t(T) * T * B * S0) : 0;
-  p->o_embtab_h = pipe.fold_embed_table ? take(size_t(T) * T * B * 64) : 0;
-  if (pipe.chains()) {
-    // merged reverse chain "readout' o latent_{L-1}'" (see Runner::backward): the readout-reverse columns that feed
-    // the last latent, and [readout-reverse columns of the earlier features (zero-padded) ; latent-reverse] stacked
-    p->o_b3a_q = take(gemm_bf16x3_words(64, S));
-    p->o_b3b_q = take(gemm_bf16x3_words(128, S * L));
-    p->o_b3c_q = take(gemm_bf16x3_words(64, u));
-  }
-  {
-    const int Hr = cfg->readout_mlp_width, H = cfg->latent_mlp_width;
-    p->o_s_wk0 = p->o_s_wt0 = 0;
-    if (pipe.slot()) {
-      auto mat = [&](int K, int N) {
-        GemmMat m;
-        m.K = K;
-        m.N = N;
-        m.w = take(size_t(K) * N);
-        m.wp = take(gemm_packed_elems(K, N));
-        m.wq = take(gemm_bf16x3_words(K, N));
-        return m;
-      };
-      p->s_g0f = mat(S, p->ng0);
-      p->s_g0ft = mat(p->ng0, S);
-      for (int l = 0; l < L; ++l) {
-        p->s_in[l] = mat(S * (l + 1) + u, H);
-        p->s_rs[l] = mat(Hr + S * (L - 1 - l), H);
-        p->s_sct[l] = mat(H, u);
-      }
-      p->s_ro0 = mat(p->SL1, Hr);
-      p->s_rstb = mat(Hr + S * L, S);
-      p->o_s_wk0 = take(size_t(S) * p->W);
-      p->o_s_wt0 = take(size_t(S) * p->W);
-    }
-  }
-  if (pipe.op_proj) {
-    auto mset = [&](int K, int N, int count) {
-      GemmMatSet m;
-      m.K = K;
-      m.N = N;
-      m.count = count;
-      auto r64 = [](size_t n) { return (n + 63) / 64 * 64; };
-      m.w_bs = r64(size_t(K) * N);
-      m.wp_bs = r64(gemm_packed_elems(K, N));
-      m.wq_bs = r64(gemm_bf16x3_words(K, N));
-      m.w = take(m.w_bs * count);
-      m.wp = take(m.wp_bs * count);
-      m.wq = take(m.wq_bs * count);
-      return m;
-    };
-    for (int l = 0; l < L; ++l) {
-      const int ka = l == 0 ? S : cfg->latent_mlp_width;
-      p->s_pr[l] = mset(ka, u, p->R);
-      p->s_prt[l] = mset(u, ka, p->R);
-    }
-    if (pipe.slot()) {
-      p->s_pr0f = mset(S, u, p->R);
-      p->s_prt0f = mset(u, S, p->R);
-    }
-  }
-  p->o_scales = take(T);
-  p->o_shifts = take(T);
-  p->n_elems = o;
+  p->blob = layout_blob(p->cfg, pipe);
   {
     void* st = nullptr;
     if (hipHostMalloc(&st, 64, hipHostMallocDefault) != hipSuccess || !st) {
@@ -948,57 +992,9 @@ extern "C" void aa_model_plan_destroy(aa_model_plan* plan) {
   delete plan;
 }
 
-extern "C" size_t aa_model_weights_bytes(const aa_model_plan* plan) { return plan ? plan->n_elems * plan->esize() : 0; }
+extern "C" size_t aa_model_weights_bytes(const aa_model_plan* plan) { return plan ? plan->blob.n_elems * plan->esize() : 0; }
 
-extern "C" uint64_t aa_model_plan_layout_hash(const aa_model_plan* p) {
-  if (!p) return 0;
-  uint64_t h = 1469598103934665603ull;  // FNV-1a over every quantity aa_model_pack_weights lays the blob out by
-  auto mix = [&](uint64_t v) {
-    for (int i = 0; i < 8; ++i) {
-      h ^= (v >> (8 * i)) & 0xff;
-      h *= 1099511628211ull;
-    }
-  };
-  auto mixv = [&](const std::vector<size_t>& v) {
-    mix(v.size());
-    for (size_t x : v) mix(x);
-  };
-  auto mixm = [&](const MlpLayout& m) {
-    mix(m.dims.size());
-    for (int d : m.dims) mix(uint64_t(d));
-    mixv(m.w); mixv(m.wt); mixv(m.wp); mixv(m.wtp); mixv(m.wq); mixv(m.wtq);
-  };
-  const aa_model_config& c = p->cfg;
-  for (uint64_t v : {uint64_t(c.dtype), uint64_t(c.num_types), uint64_t(c.num_bessels), uint64_t(c.l_max), uint64_t(c.num_layers),
-                     uint64_t(c.num_scalar), uint64_t(c.num_tensor), uint64_t(c.embed_dim), uint64_t(c.embed_mlp_width),
-                     uint64_t(c.latent_mlp_width), uint64_t(c.readout_mlp_width), uint64_t(p->u_raw), uint64_t(p->pipe.channel_minor()),
-                     uint64_t(p->pipe.env_moments()), uint64_t(p->pipe.chains()), uint64_t(p->pipe.chain_pair + 1), uint64_t(p->pipe.tp_op + 1), uint64_t(p->ng0),
-                     uint64_t(p->n_elems), uint64_t(p->pipe.slot())})
-    mix(v);
-  if (p->pipe.slot()) {
-    auto mixm = [&](const GemmMat& m) { mix(m.w); mix(m.wp); mix(m.wq); };
-    mixm(p->s_g0f); mixm(p->s_g0ft); mixm(p->s_ro0); mixm(p->s_rstb);
-    for (int l = 0; l < c.num_layers; ++l) { mixm(p->s_in[l]); mixm(p->s_rs[l]); mixm(p->s_sct[l]); }
-    mix(p->o_s_wk0); mix(p->o_s_wt0);
-  }
-  if (p->pipe.op_proj) {
-    auto mixs = [&](const GemmMatSet& m) { mix(m.w); mix(m.wp); mix(m.wq); mix(m.w_bs); };
-    for (int l = 0; l < c.num_layers; ++l) { mixs(p->s_pr[l]); mixs(p->s_prt[l]); }
-    mixs(p->s_pr0f); mixs(p->s_prt0f);
-  }
-  for (size_t v : {p->o_rmax, p->o_bessel, p->o_cemb, p->o_nemb, p->o_basis, p->o_g0, p->o_g0t, p->o_g0p, p->o_g0tp, p->o_g0q, p->o_g0tq,
-                   p->o_b3a_q, p->o_b3b_q, p->o_b3c_q, p->o_ro_last, p->o_scales, p->o_shifts, p->o_embtab, p->o_embtab_h, p->o_lat1in_fq, p->o_ro0_fq, p->o_b3af_q, p->o_b3bf_q, p->o_g0fq, p->o_g0tfq, p->o_wk0f, p->o_wt0f})
-    mix(v);
-  for (int l = 0; l < c.num_layers; ++l) {
-    mix(p->o_tpw[l]);
-    mix(p->pipe.env_moments() ? p->o_wk[l] : 0);
-    mix(p->pipe.env_moments() ? p->o_wt[l] : 0);
-    mixm(p->latent[l]);
-  }
-  mixm(p->embed);
-  mixm(p->readout);
-  return h ? h : 1;
-}
+extern "C" uint64_t aa_model_plan_layout_hash(const aa_model_plan* p) { return p ? p->blob.hash(p->cfg, p->pipe, p->u_raw) : 0; }
 
 // alpha_i of nequip ScalarMLPFunction: c_prev / sqrt(fan_in | fan_out)
 // `which`: 0 scalar_embed_mlp, 1 latent MLPs, 2 edge_readout (their nonlinearities may differ); linear maps pass -1
@@ -1012,78 +1008,131 @@ static double mlp_alpha(const aa_model_config& c, int layer, int din, int dout, 
   return norm / std::sqrt(double(c.forward_weight_init ? din : dout));
 }
 
-extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_weights* raw_in, void* dev_blob,
-                                     size_t blob_bytes, aa_stream stream) {
-  AA_REQUIRE(p && raw_in && dev_blob, "aa_model_pack_weights: null argument");
-  AA_REQUIRE(blob_bytes >= aa_model_weights_bytes(p), "aa_model_pack_weights: blob too small");
-  const aa_model_config& c = p->cfg;
-  const int S = c.num_scalar, u = c.num_tensor, L = c.num_layers, T = c.num_types, B = c.num_bessels, S0 = c.embed_dim;
-  const int W = p->W;
-  // Channel-padded plan (aa_model_plan_create): the state_dict tensors carry u_raw channels; build zero-padded copies in
-  // the reference's own layouts so that everything below indexes a u-channel model.  The ScalarMLPFunction constants
-  // (alpha = c / sqrt(fan_in | fan_out)) keep following the TRUE layer shapes (the *_raw widths).
-  const int u_raw = p->u_raw, Rp = p->R, dlat = c.latent_mlp_depth;
-  const int We_in = (c.env_shared_weights != 0) ? u_raw : Rp * u_raw;   // env columns in the state_dict
-  const int We_pad = (c.env_shared_weights != 0) ? u : W;
-  const int dW = W - Rp * u_raw, dWe = We_pad - We_in, du = u - u_raw;  // how much wider the padded shapes are
-  const int dHe = c.embed_mlp_width - p->hid_raw[0], dHl = c.latent_mlp_width - p->hid_raw[1], dHr = c.readout_mlp_width - p->hid_raw[2];
-  aa_model_raw_weights raw_local = *raw_in;
+// ------------------------------------------------------------------------------------------------
+// packing: raw state_dict tensors -> the blob (host arithmetic only: pack_blob_host), then one upload (aa_model_pack_weights)
+// ------------------------------------------------------------------------------------------------
+// C[M,N] = A[M,K] . B[K,N] in fp64, row-major with leading dimensions lda / ldb.  Every element of C is ONE accumulator that starts at
+// 0.0 and takes A[i][k] * B[k][j] in ascending k -- the blob is pinned byte by byte (tests/test_weight_blob.py), so no blocking and
+// no pairwise sums here.  (k is the middle loop only so that B is read along its rows.)
+static std::vector<double> matmul(const double* A, int lda, const double* B, int ldb, int M, int K, int N) {
+  std::vector<double> C(size_t(M) * N, 0.0);
+  for (int i = 0; i < M; ++i)
+    for (int k = 0; k < K; ++k) {
+      const double a = A[size_t(i) * lda + k];
+      for (int j = 0; j < N; ++j) C[size_t(i) * N + j] += a * B[size_t(k) * ldb + j];
+    }
+  return C;
+}
+
+// [M,N] row-major -> [N,M]
+static std::vector<double> transposed(const double* A, int M, int N) {
+  std::vector<double> t(size_t(M) * N);
+  for (int i = 0; i < M; ++i)
+    for (int j = 0; j < N; ++j) t[size_t(j) * M + i] = A[size_t(i) * N + j];
+  return t;
+}
+
+// One pack: the plan's layout (read only), the caller's tensors, and the blob in fp64 while it is being filled.  run() is the
+// sequence of steps; each step writes entries of the layout and reads only raw tensors or entries an earlier step wrote.
+struct Packer {
+  const aa_model_plan& p;
+  aa_model_raw_weights raw;  // the caller's tensors; zero-padded copies (pad_store) where the plan is wider than the model
+  const BlobLayout& b = p.blob;
+  const aa_model_config& c = p.cfg;
+  const ModelPipeline& pipe = p.pipe;
+  const int S = c.num_scalar, u = c.num_tensor, L = c.num_layers, T = c.num_types, B = c.num_bessels, S0 = c.embed_dim, R = p.R, W = p.W;
+  // env-weight columns: reference layout [u][R] (_channels.py:46-51); the specialised kernels want [R][u].
+  // With weight_individual_irreps=False the Allegro layers' env weights are [u] in the reference (_channels.py:29-31,
+  // 60-63: one weight per channel for all irreps): the packed matrices replicate that column for every irrep, which
+  // is the same linear map, so every kernel runs unchanged.  (The tensor-embedding weights w0 are always individual,
+  // tensorembed.py:76-81.)
+  const bool shared = c.env_shared_weights != 0;
+  const int We_in = shared ? p.u_raw : R * p.u_raw, We = shared ? u : W;  // env-weight columns of first_proj / latent outputs in the state_dict, and zero-padded to the plan's channels
+  // how much wider the plan's (padded) shapes are than the model's: the ScalarMLPFunction constants (alpha = c / sqrt(fan_in | fan_out))
+  // keep following the TRUE layer shapes
+  const int du = u - p.u_raw, dW = W - R * p.u_raw, dWe = We - We_in, dHe = c.embed_mlp_width - p.hid_raw[0],
+            dHl = c.latent_mlp_width - p.hid_raw[1], dHr = c.readout_mlp_width - p.hid_raw[2];
   std::vector<std::vector<double>> pad_store;
+  std::vector<double> stage;  // fp32 plans: the fp64 blob before rounding (fp64 plans fill the output bytes directly)
+  double* h = nullptr;        // the blob in fp64, b.n_elems elements, zero where nothing is written
+  std::vector<double> g0f, wenv0f;         // fold_embed_output(): W1 @ G0 [He, ng0] and W1 @ Wenv0 [He, R u]
+  std::vector<const GemmMat*> slot_mats;   // (fp32 plans: their bf16x3 copies are split off the rounded matrices)
+  std::vector<const GemmMatSet*> proj_sets;
+
+  void put(size_t off, const double* src, size_t n, double scale) {
+    for (size_t i = 0; i < n; ++i) h[off + i] = src[i] * scale;
+  }
+  // a [rows, cols] product and its transpose
+  void put_with_transpose(size_t off, size_t off_t, const std::vector<double>& m, int rows, int cols) {
+    std::copy(m.begin(), m.end(), h + off);
+    const std::vector<double> t = transposed(m.data(), rows, cols);
+    std::copy(t.begin(), t.end(), h + off_t);
+  }
+  int w0_col(int q) const { return pipe.channel_minor() ? (q % u) * R + q / u : q; }  // packed col q <- reference col
+  int env_col(int q) const {
+    const int ch = pipe.channel_minor() ? q % u : q / R, r = pipe.channel_minor() ? q / u : q % R;
+    return shared ? ch : ch * R + r;
+  }
+
   // zero-extend a row-major [r_raw][c_raw] matrix to [r_pad][c_pad] (every padded block is a suffix: both env layouts are
   // channel-major -- [u][R] or [u] -- and hidden units / scalar rows are appended at the end)
-  auto pad2d = [&](const double* src, int r_raw, int c_raw, int r_pad, int c_pad) -> const double* {
+  const double* pad2d(const double* src, int r_raw, int c_raw, int r_pad, int c_pad) {
     if (r_raw == r_pad && c_raw == c_pad) return src;
     pad_store.emplace_back(size_t(r_pad) * c_pad, 0.0);
     std::vector<double>& d = pad_store.back();
     for (int r = 0; r < r_raw; ++r)
       for (int q = 0; q < c_raw; ++q) d[size_t(r) * c_pad + q] = src[size_t(r) * c_raw + q];
     return d.data();
-  };
-  if (du || dHe || dHl || dHr) {
-    AA_REQUIRE(raw_in->env_embed_linear && raw_in->first_proj, "pack: missing embedding weights");
-    raw_local.env_embed_linear = pad2d(raw_in->env_embed_linear, S, Rp * u_raw, S, W);
-    raw_local.first_proj = pad2d(raw_in->first_proj, S, S + We_in, S, S + We_pad);
+  }
+
+  // Channel-padded plan (choose_pipeline): the state_dict tensors carry u_raw channels; build zero-padded copies in
+  // the reference's own layouts so that everything below indexes a u-channel model.
+  int pad_raw() {
+    if (!(du || dHe || dHl || dHr)) return AA_OK;
+    const aa_model_raw_weights in = raw;
+    const int u_raw = p.u_raw, dlat = c.latent_mlp_depth, H = c.latent_mlp_width;
+    AA_REQUIRE(in.env_embed_linear && in.first_proj, "pack: missing embedding weights");
+    raw.env_embed_linear = pad2d(in.env_embed_linear, S, R * u_raw, S, W);
+    raw.first_proj = pad2d(in.first_proj, S, S + We_in, S, S + We);
     if (dHe) {  // (only single-hidden-layer MLPs are padded)
-      AA_REQUIRE(raw_in->embed_mlp[0] && raw_in->embed_mlp[1], "pack: missing scalar_embed_mlp weights");
-      raw_local.embed_mlp[0] = pad2d(raw_in->embed_mlp[0], S0, p->hid_raw[0], S0, c.embed_mlp_width);
-      raw_local.embed_mlp[1] = pad2d(raw_in->embed_mlp[1], p->hid_raw[0], S, c.embed_mlp_width, S);
+      AA_REQUIRE(in.embed_mlp[0] && in.embed_mlp[1], "pack: missing scalar_embed_mlp weights");
+      raw.embed_mlp[0] = pad2d(in.embed_mlp[0], S0, p.hid_raw[0], S0, c.embed_mlp_width);
+      raw.embed_mlp[1] = pad2d(in.embed_mlp[1], p.hid_raw[0], S, c.embed_mlp_width, S);
     }
     for (int l = 0; l < L; ++l) {
-      AA_REQUIRE(raw_in->latent[l][0] && raw_in->latent[l][dlat] && raw_in->tp_weights[l], "pack: missing latent / tp weights");
-      const int out_raw = S + (l < L - 1 ? We_in : 0), out_pad = S + (l < L - 1 ? We_pad : 0);
+      AA_REQUIRE(in.latent[l][0] && in.latent[l][dlat] && in.tp_weights[l], "pack: missing latent / tp weights");
+      const int out_raw = S + (l < L - 1 ? We_in : 0), out_pad = S + (l < L - 1 ? We : 0);
       if (dlat == 0) {
-        raw_local.latent[l][0] = pad2d(raw_in->latent[l][0], S * (l + 1) + u_raw, out_raw, S * (l + 1) + u, out_pad);
+        raw.latent[l][0] = pad2d(in.latent[l][0], S * (l + 1) + u_raw, out_raw, S * (l + 1) + u, out_pad);
       } else {
         // first layer: input rows [S (l + 1) | u scalars], output = hidden units; last layer: [hidden][S | env columns]
-        raw_local.latent[l][0] = pad2d(raw_in->latent[l][0], S * (l + 1) + u_raw, dlat == 1 ? p->hid_raw[1] : c.latent_mlp_width,
-                                       S * (l + 1) + u, c.latent_mlp_width);
-        raw_local.latent[l][dlat] = pad2d(raw_in->latent[l][dlat], dlat == 1 ? p->hid_raw[1] : c.latent_mlp_width, out_raw, c.latent_mlp_width, out_pad);
+        const int H_raw = dlat == 1 ? p.hid_raw[1] : H;
+        raw.latent[l][0] = pad2d(in.latent[l][0], S * (l + 1) + u_raw, H_raw, S * (l + 1) + u, H);
+        raw.latent[l][dlat] = pad2d(in.latent[l][dlat], H_raw, out_raw, H, out_pad);
       }
-      if (c.tps[l].coupling) raw_local.tp_weights[l] = pad2d(raw_in->tp_weights[l], u_raw, c.tps[l].num_paths, u, c.tps[l].num_paths);
+      if (c.tps[l].coupling) raw.tp_weights[l] = pad2d(in.tp_weights[l], u_raw, c.tps[l].num_paths, u, c.tps[l].num_paths);
     }
     if (dHr) {
-      AA_REQUIRE(raw_in->readout[0] && raw_in->readout[1], "pack: missing readout weights");
-      raw_local.readout[0] = pad2d(raw_in->readout[0], p->SL1, p->hid_raw[2], p->SL1, c.readout_mlp_width);
-      raw_local.readout[1] = pad2d(raw_in->readout[1], p->hid_raw[2], 1, c.readout_mlp_width, 1);
+      AA_REQUIRE(in.readout[0] && in.readout[1], "pack: missing readout weights");
+      raw.readout[0] = pad2d(in.readout[0], p.SL1, p.hid_raw[2], p.SL1, c.readout_mlp_width);
+      raw.readout[1] = pad2d(in.readout[1], p.hid_raw[2], 1, c.readout_mlp_width, 1);
     }
+    return AA_OK;
   }
-  const aa_model_raw_weights* raw = &raw_local;
-  std::vector<double> h(p->n_elems, 0.0);
-  auto copy = [&](size_t off, const double* src, size_t n, double scale) {
-    for (size_t i = 0; i < n; ++i) h[off + i] = src[i] * scale;
-  };
-  AA_REQUIRE(raw->rmax_recip && raw->env_embed_linear && raw->first_proj, "pack: missing embedding weights");
-  copy(p->o_rmax, raw->rmax_recip, size_t(T) * T, 1.0);
-  if (c.embed_kind == 1) {
-    // [class][c][s] (spline.py:69-71) -> basis-major [class][s][c]
-    AA_REQUIRE(raw->spline_weights, "pack: missing spline weights");
-    for (int cls = 0; cls < T * T; ++cls)
-      for (int cc = 0; cc < S0; ++cc)
-        for (int n = 0; n < B; ++n)
-          h[p->o_embtab + (size_t(cls) * B + n) * S0 + cc] = raw->spline_weights[(size_t(cls) * S0 + cc) * B + n];
-  } else {
-    AA_REQUIRE(raw->bessel_weights && raw->center_embed && raw->neighbor_embed && raw->basis_linear,
-               "pack: missing embedding weights");
+
+  // cutoffs, radial basis, type embedding; the two-body table where the pipeline carries one
+  int pack_embedding() {
+    AA_REQUIRE(raw.rmax_recip && raw.env_embed_linear && raw.first_proj, "pack: missing embedding weights");
+    put(b.o_rmax, raw.rmax_recip, size_t(T) * T, 1.0);
+    if (c.embed_kind == 1) {
+      // [class][c][s] (spline.py:69-71) -> basis-major [class][s][c]
+      AA_REQUIRE(raw.spline_weights, "pack: missing spline weights");
+      for (int cls = 0; cls < T * T; ++cls)
+        for (int cc = 0; cc < S0; ++cc)
+          for (int n = 0; n < B; ++n) h[b.o_embtab + (size_t(cls) * B + n) * S0 + cc] = raw.spline_weights[(size_t(cls) * S0 + cc) * B + n];
+      return AA_OK;
+    }
+    AA_REQUIRE(raw.bessel_weights && raw.center_embed && raw.neighbor_embed && raw.basis_linear, "pack: missing embedding weights");
     // Two published conventions of nequip's BesselEdgeLengthEncoding (EXT; which one a given nequip release uses
     // cannot be checked in this container -- DESIGN.md section 6): (a) bessel_weights = n pi, basis sin(w x) / x;
     // (b) bessel_weights = n (linspace(1, B, B)), basis sinc(x w) w = sin(pi w x) / (pi x).  Both are served by the
@@ -1095,8 +1144,8 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
       bool is_n = true, is_npi = true;
       for (int n = 0; n < B; ++n) {
         // (relative 1e-5: the roots of an fp32 state_dict are n*pi rounded to fp32)
-        is_n = is_n && std::fabs(raw->bessel_weights[n] - double(n + 1)) < 1e-5 * double(n + 1);
-        is_npi = is_npi && std::fabs(raw->bessel_weights[n] - double(n + 1) * kPi) < 1e-5 * double(n + 1) * kPi;
+        is_n = is_n && std::fabs(raw.bessel_weights[n] - double(n + 1)) < 1e-5 * double(n + 1);
+        is_npi = is_npi && std::fabs(raw.bessel_weights[n] - double(n + 1) * kPi) < 1e-5 * double(n + 1) * kPi;
       }
       if (!is_n && !is_npi)
         return fail(AA_ERR_INVALID, "pack: bessel_weights are neither n nor n*pi (trained roots?): state aa_model_config.bessel_convention (1: sin(w x)/x, 2: sinc)");
@@ -1104,24 +1153,23 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
     } else if (c.bessel_convention != 1 && c.bessel_convention != 2) {
       return fail(AA_ERR_INVALID, "pack: bessel_convention must be 0 (recognise), 1 (roots n*pi) or 2 (sinc form)");
     }
-    copy(p->o_bessel, raw->bessel_weights, B, sinc_form ? kPi : 1.0);
-    copy(p->o_cemb, raw->center_embed, size_t(T) * S0 / 2, 1.0);
-    copy(p->o_nemb, raw->neighbor_embed, size_t(T) * S0 / 2, 1.0);
-    copy(p->o_basis, raw->basis_linear, size_t(B) * S0, mlp_alpha(c, 0, B, S0) * (sinc_form ? 1.0 / kPi : 1.0));
+    put(b.o_bessel, raw.bessel_weights, B, sinc_form ? kPi : 1.0);
+    put(b.o_cemb, raw.center_embed, size_t(T) * S0 / 2, 1.0);
+    put(b.o_nemb, raw.neighbor_embed, size_t(T) * S0 / 2, 1.0);
+    put(b.o_basis, raw.basis_linear, size_t(B) * S0, mlp_alpha(c, 0, B, S0) * (sinc_form ? 1.0 / kPi : 1.0));
+    if (pipe.two_body_table) {
+      const int half = S0 / 2;
+      for (int ti = 0; ti < T; ++ti)
+        for (int tj = 0; tj < T; ++tj)
+          for (int n = 0; n < B; ++n)
+            for (int cc = 0; cc < S0; ++cc) {
+              const double te = cc < half ? h[b.o_cemb + size_t(ti) * half + cc] : h[b.o_nemb + size_t(tj) * half + (cc - half)];
+              h[b.o_embtab + ((size_t(ti) * T + tj) * B + n) * S0 + cc] = te * h[b.o_basis + size_t(n) * S0 + cc];
+            }
+    }
+    return AA_OK;
   }
-  // env-weight columns: reference layout [u][R] (_channels.py:46-51); the specialised kernels want [R][u].
-  // With weight_individual_irreps=False the Allegro layers' env weights are [u] in the reference (_channels.py:29-31,
-  // 60-63: one weight per channel for all irreps): the packed matrices replicate that column for every irrep, which
-  // is the same linear map, so every kernel runs unchanged.  (The tensor-embedding weights w0 are always individual,
-  // tensorembed.py:76-81.)
-  const int Rr = p->R;
-  const bool shared = c.env_shared_weights != 0;
-  const int We = shared ? u : W;  // env-weight columns of first_proj / latent outputs in the state_dict
-  auto w0_col = [&](int q) { return p->pipe.channel_minor() ? (q % u) * Rr + q / u : q; };  // packed col q <- reference col
-  auto env_col = [&](int q) {
-    const int ch = p->pipe.channel_minor() ? q % u : q / Rr, r = p->pipe.channel_minor() ? q / u : q % Rr;
-    return shared ? ch : ch * Rr + r;
-  };
+
   // pack an MLP; if env_off >= 0 the LAST layer's columns [env_off, env_off+W) are env weights
   // raw_last_width: true column count of the LAST layer in the state_dict (>= packed width when the env columns
   // are split off for the moments path); alpha always follows the reference's full layer shape
@@ -1129,8 +1177,8 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
   // (channel-padded) shapes packed here -- alpha follows the reference
   // hidden_less: by how much the (single) hidden layer was widened -- layer 0's fan_out and layer 1's fan_in are narrower
   // in the reference.  `total_layers`: layers of the whole MLP (the readout packs only its first ones here).
-  auto pack_mlp = [&](const MlpLayout& m, const double* const* ws, int nlayers, int env_off, int which, int raw_last_width = -1,
-                      int true_din_less = 0, int true_dout_less = 0, int hidden_less = 0, int total_layers = -1) -> bool {
+  bool pack_mlp(const MlpLayout& m, const double* const* ws, int nlayers, int env_off, int which, int raw_last_width = -1,
+                int true_din_less = 0, int true_dout_less = 0, int hidden_less = 0, int total_layers = -1) {
     if (total_layers < 0) total_layers = nlayers;
     for (int i = 0; i < nlayers; ++i) {
       if (!ws[i]) return false;
@@ -1150,215 +1198,171 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
       gemm_pack_b(&h[m.wt[i]], dout, din, &h[m.wtp[i]]);
     }
     return true;
-  };
-  AA_REQUIRE(pack_mlp(p->embed, raw->embed_mlp, c.embed_mlp_depth + 1, -1, 0, -1, 0, 0, dHe), "pack: missing scalar_embed_mlp weights");
-  {
-    // fused first stage: [ two_body (first_proj[:, :S]) | w0 (env_embed_linear) | env_w0 (first_proj[:, S:]) ]
-    // (moments path: the env_w0 columns are not part of the GEMM; they become Wenv of layer 0 below)
-    const int NG = p->ng0;
+  }
+
+  // fused first stage: [ two_body (first_proj[:, :S]) | w0 (env_embed_linear) | env_w0 (first_proj[:, S:]) ]
+  // (moments path: the env_w0 columns are not part of the GEMM; they become Wenv of layer 0, pack_env_weights)
+  void pack_first_stage() {
+    const int NG = b.ng0;
     double a_env = mlp_alpha(c, 0, S, W - dW), a_proj = mlp_alpha(c, 0, S, S + We - dWe);
     for (int r = 0; r < S; ++r)
       for (int q = 0; q < NG; ++q) {
         double v;
         if (q < S)
-          v = raw->first_proj[size_t(r) * (S + We) + q] * a_proj;
+          v = raw.first_proj[size_t(r) * (S + We) + q] * a_proj;
         else if (q < S + W)
-          v = raw->env_embed_linear[size_t(r) * W + w0_col(q - S)] * a_env;
+          v = raw.env_embed_linear[size_t(r) * W + w0_col(q - S)] * a_env;
         else
-          v = raw->first_proj[size_t(r) * (S + We) + S + env_col(q - S - W)] * a_proj;
-        h[p->o_g0 + size_t(r) * NG + q] = v;
-        h[p->o_g0t + size_t(q) * S + r] = v;
+          v = raw.first_proj[size_t(r) * (S + We) + S + env_col(q - S - W)] * a_proj;
+        h[b.o_g0 + size_t(r) * NG + q] = v;
+        h[b.o_g0t + size_t(q) * S + r] = v;
       }
-    gemm_pack_b(&h[p->o_g0], S, NG, &h[p->o_g0p]);
-    gemm_pack_b(&h[p->o_g0t], NG, S, &h[p->o_g0tp]);
+    gemm_pack_b(&h[b.o_g0], S, NG, &h[b.o_g0p]);
+    gemm_pack_b(&h[b.o_g0t], NG, S, &h[b.o_g0tp]);
   }
-  for (int l = 0; l < L; ++l) {
-    AA_REQUIRE(pack_mlp(p->latent[l], raw->latent[l], c.latent_mlp_depth + 1, (l < L - 1 && !p->pipe.env_moments()) ? S : -1, 1,
-                        S + (l < L - 1 ? We : 0), du, l < L - 1 ? dWe : 0, dHl),
-               "pack: missing latent weights");
-    AA_REQUIRE(raw->tp_weights[l], "pack: missing tp weights");
-    copy(p->o_tpw[l], raw->tp_weights[l], size_t(c.tps[l].coupling ? u : 1) * c.tps[l].num_paths, 1.0);
+
+  // the three MLP stacks with the ScalarMLPFunction constants applied, the first stage, tensor-product weights, scales and shifts
+  int pack_mlps() {
+    AA_REQUIRE(pack_mlp(b.embed, raw.embed_mlp, c.embed_mlp_depth + 1, -1, 0, -1, 0, 0, dHe), "pack: missing scalar_embed_mlp weights");
+    pack_first_stage();
+    for (int l = 0; l < L; ++l) {
+      AA_REQUIRE(pack_mlp(b.latent[l], raw.latent[l], c.latent_mlp_depth + 1, (l < L - 1 && !pipe.env_moments()) ? S : -1, 1,
+                          S + (l < L - 1 ? We : 0), du, l < L - 1 ? dWe : 0, dHl),
+                 "pack: missing latent weights");
+      AA_REQUIRE(raw.tp_weights[l], "pack: missing tp weights");
+      put(b.o_tpw[l], raw.tp_weights[l], size_t(c.tps[l].coupling ? u : 1) * c.tps[l].num_paths, 1.0);
+    }
+    pack_env_weights();
+    AA_REQUIRE(pack_mlp(b.readout, raw.readout, c.readout_mlp_depth, -1, 2, -1, 0, 0, dHr, c.readout_mlp_depth + 1), "pack: missing readout weights");
+    const double* wl = raw.readout[c.readout_mlp_depth];
+    AA_REQUIRE(wl, "pack: missing readout weights");
+    put(b.o_ro_last, wl, b.ro_last_dim, mlp_alpha(c, c.readout_mlp_depth, b.ro_last_dim - (c.readout_mlp_depth > 0 ? dHr : 0), 1, 2));
+    if (c.has_scales) {
+      AA_REQUIRE(raw.scales, "pack: missing scales");
+      put(b.o_scales, raw.scales, T, 1.0);
+    }
+    if (c.has_shifts) {
+      AA_REQUIRE(raw.shifts, "pack: missing shifts");
+      put(b.o_shifts, raw.shifts, T, 1.0);
+    }
+    return AA_OK;
   }
-  if (p->pipe.env_moments()) {
-    // Wenv_l[k][r][ch] (and its [r][ch][k] transpose) from the reference's [k][S + ch*R + r] columns
+
+  // (moments / operator plans) Wenv_l[k][r][ch] and its [r][ch][k] transpose from the reference's [k][S + ch*R + r] columns
+  void pack_env_weights() {
+    if (!pipe.env_moments()) return;
     auto fill = [&](int l, const double* rawm, int ka, int raw_w, double al) {
       for (int k = 0; k < ka; ++k)
-        for (int r = 0; r < Rr; ++r)
+        for (int r = 0; r < R; ++r)
           for (int ch = 0; ch < u; ++ch) {
-            double v = rawm[size_t(k) * raw_w + S + (shared ? ch : ch * Rr + r)] * al;
-            h[p->o_wk[l] + (size_t(k) * Rr + r) * u + ch] = v;
-            h[p->o_wt[l] + (size_t(r) * u + ch) * ka + k] = v;
+            double v = rawm[size_t(k) * raw_w + S + (shared ? ch : ch * R + r)] * al;
+            h[b.o_wk[l] + (size_t(k) * R + r) * u + ch] = v;
+            h[b.o_wt[l] + (size_t(r) * u + ch) * ka + k] = v;
           }
     };
-    fill(0, raw->first_proj, S, S + We, mlp_alpha(c, 0, S, S + We - dWe));
+    fill(0, raw.first_proj, S, S + We, mlp_alpha(c, 0, S, S + We - dWe));
     const int dl = c.latent_mlp_depth;  // index of a latent's last layer
     for (int l = 1; l < L; ++l)
-      fill(l, raw->latent[l - 1][dl], c.latent_mlp_width, S + We, mlp_alpha(c, dl, c.latent_mlp_width - dHl, S + We - dWe, 1));
+      fill(l, raw.latent[l - 1][dl], c.latent_mlp_width, S + We, mlp_alpha(c, dl, c.latent_mlp_width - dHl, S + We - dWe, 1));
   }
-  AA_REQUIRE(pack_mlp(p->readout, raw->readout, c.readout_mlp_depth, -1, 2, -1, 0, 0, dHr, c.readout_mlp_depth + 1), "pack: missing readout weights");
-  {
-    const double* wl = raw->readout[c.readout_mlp_depth];
-    AA_REQUIRE(wl, "pack: missing readout weights");
-    copy(p->o_ro_last, wl, p->ro_last_dim, mlp_alpha(c, c.readout_mlp_depth, p->ro_last_dim - (c.readout_mlp_depth > 0 ? dHr : 0), 1, 2));
+
+  // The output layer W1 [He, S] of scalar_embed_mlp folded into its two consumers, formed once for the chains pipeline
+  // (fold_embed_output, He = 64) and the slot form (He = S): W1 @ G0 and Wenv0'[k][r][ch] = sum_m W1[k][m] Wenv0[m][r][ch]
+  void fold_embed_output() {
+    const int De = c.embed_mlp_depth;
+    const double* w1 = &h[b.embed.w[De]];
+    g0f = matmul(w1, S, &h[b.o_g0], b.ng0, b.embed.dims[De], S, b.ng0);
+    wenv0f = matmul(w1, S, &h[b.o_wk[0]], W, b.embed.dims[De], S, W);
   }
-  if (c.has_scales) {
-    AA_REQUIRE(raw->scales, "pack: missing scales");
-    copy(p->o_scales, raw->scales, T, 1.0);
+
+  // F(j -> consumer) = Wout_j [H, S] @ Wc[S (j+1) .. S (j+2)) [S, Nc]: the consumer's row block of lat_j behind latent j's output layer
+  std::vector<double> fold_block(int j, const double* wc, int Nc) const {
+    return matmul(&h[b.latent[j].w[1]], S, wc + size_t(S) * (j + 1) * Nc, Nc, c.latent_mlp_width, S, Nc);
   }
-  if (c.has_shifts) {
-    AA_REQUIRE(raw->shifts, "pack: missing shifts");
-    copy(p->o_shifts, raw->shifts, T, 1.0);
+  // ... in place, in a copy f [., Nc] of the consumer's first layer (S = H wherever a layer is folded, so the block keeps its size)
+  void fold_rows(std::vector<double>& f, int j, int Nc) const {
+    const std::vector<double> blk = fold_block(j, f.data(), Nc);
+    std::copy(blk.begin(), blk.end(), f.begin() + size_t(S) * (j + 1) * Nc);
   }
-  if (p->pipe.two_body_table && c.embed_kind == 0) {
-    const int half = S0 / 2;
-    for (int ti = 0; ti < T; ++ti)
-      for (int tj = 0; tj < T; ++tj)
-        for (int n = 0; n < B; ++n)
-          for (int cc = 0; cc < S0; ++cc) {
-            const double te = cc < half ? h[p->o_cemb + size_t(ti) * half + cc] : h[p->o_nemb + size_t(tj) * half + (cc - half)];
-            h[p->o_embtab + ((size_t(ti) * T + tj) * B + n) * S0 + cc] = te * h[p->o_basis + size_t(n) * S0 + cc];
-          }
-  }
-  if (p->pipe.fold_embed_output) {
-    // (fold_embed_output) env weights of layer 0 behind the output layer of scalar_embed_mlp: Wenv0'[k][r][ch] = sum_m W1[k][m] Wenv0[m][r][ch]
-    const double* w1 = &h[p->embed.w[1]];  // [64, S]
-    const int Rr_ = p->R, uu = c.num_tensor;
-    for (int k = 0; k < 64; ++k)
-      for (int r = 0; r < Rr_; ++r)
-        for (int ch = 0; ch < uu; ++ch) {
-          double v = 0.0;
-          for (int m = 0; m < S; ++m) v += w1[size_t(k) * S + m] * h[p->o_wk[0] + (size_t(m) * Rr_ + r) * uu + ch];
-          h[p->o_wk0f + (size_t(k) * Rr_ + r) * uu + ch] = v;
-          h[p->o_wt0f + (size_t(r) * uu + ch) * 64 + k] = v;
-        }
-  }
-  if (p->pipe.fold_embed_table) {
-    // T[pair][n][k] = sum_c tab[pair][n][c] * W0[c][k]  (W0: the packed first layer of scalar_embed_mlp, normalisation folded)
-    const int H = p->embed.dims[1];
-    for (int cls = 0; cls < T * T; ++cls)
-      for (int n = 0; n < B; ++n)
-        for (int k = 0; k < H; ++k) {
-          double acc = 0.0;
-          for (int cc = 0; cc < S0; ++cc) acc += h[p->o_embtab + (size_t(cls) * B + n) * S0 + cc] * h[p->embed.w[0] + size_t(cc) * H + k];
-          h[p->o_embtab_h + (size_t(cls) * B + n) * H + k] = acc;
-        }
-  }
-  std::vector<const GemmMat*> slot_mats;  // (fp32 plans: bf16x3 copies are split off the rounded matrices below)
-  if (p->pipe.slot()) {
-    // slot form: every matrix below is a product / regrouping of the NORMALISED matrices packed above, formed in fp64
-    const int De = c.embed_mlp_depth, Hr = c.readout_mlp_width, H = c.latent_mlp_width, NG = p->ng0, SL1 = p->SL1;
-    auto put = [&](const GemmMat& m, const std::vector<double>& d) {
-      std::copy(d.begin(), d.end(), h.begin() + m.w);
-      gemm_pack_b(&h[m.w], m.K, m.N, &h[m.wp]);
-      slot_mats.push_back(&m);
-    };
-    const double* w1 = &h[p->embed.w[De]];  // [S(=He), S] output layer of scalar_embed_mlp
-    {
-      std::vector<double> gf(size_t(S) * NG), gft(size_t(NG) * S);
-      for (int k = 0; k < S; ++k)
-        for (int q = 0; q < NG; ++q) {
-          double v = 0.0;
-          for (int m = 0; m < S; ++m) v += w1[size_t(k) * S + m] * h[p->o_g0 + size_t(m) * NG + q];
-          gf[size_t(k) * NG + q] = v;
-          gft[size_t(q) * S + k] = v;
-        }
-      put(p->s_g0f, gf);
-      put(p->s_g0ft, gft);
-      for (int k = 0; k < S; ++k)
-        for (int r = 0; r < Rr; ++r)
-          for (int ch = 0; ch < u; ++ch) {
-            double v = 0.0;
-            for (int m = 0; m < S; ++m) v += w1[size_t(k) * S + m] * h[p->o_wk[0] + (size_t(m) * Rr + r) * u + ch];
-            h[p->o_s_wk0 + (size_t(k) * Rr + r) * u + ch] = v;
-            h[p->o_s_wt0 + (size_t(r) * u + ch) * S + k] = v;
-          }
+
+  // (fp64 part of the chains pipeline's folds; the bf16x3 ones follow the rounding: pack_chain_folds)
+  void pack_embed_folds() {
+    if (pipe.fold_embed_output) put_with_transpose(b.o_wk0f, b.o_wt0f, wenv0f, 64, W);  // as [k][R][u] and [R][u][k]
+    if (pipe.fold_embed_table) {
+      // T[pair][n][k] = sum_c tab[pair][n][c] * W0[c][k]  (W0: the packed first layer of scalar_embed_mlp, normalisation folded)
+      const int H = b.embed.dims[1];
+      const std::vector<double> t = matmul(&h[b.o_embtab], S0, &h[b.embed.w[0]], H, T * T * B, S0, H);
+      std::copy(t.begin(), t.end(), h + b.o_embtab_h);
     }
-    // F(j -> consumer)[m][n] = sum_q Wout_j[m][q] Wc[S (j+1) + q][n]: the consumer's row block of lat_j behind latent j's output layer
-    auto fold_block = [&](int j, const double* wc, int Nc, std::vector<double>& out /* [H][Nc] */) {
-      const double* wo = &h[p->latent[j].w[1]];  // [H, S]
-      out.assign(size_t(H) * Nc, 0.0);
-      for (int m = 0; m < H; ++m)
-        for (int q = 0; q < S; ++q) {
-          const double a = wo[size_t(m) * S + q];
-          const double* row = wc + size_t(S * (j + 1) + q) * Nc;
-          for (int n = 0; n < Nc; ++n) out[size_t(m) * Nc + n] += a * row[n];
-        }
-    };
-    std::vector<double> blk;
-    // forward: folded first layers
+  }
+
+  void put_slot(const GemmMat& m, const std::vector<double>& d) {
+    std::copy(d.begin(), d.end(), h + m.w);
+    gemm_pack_b(&h[m.w], m.K, m.N, &h[m.wp]);
+    slot_mats.push_back(&m);
+  }
+
+  // slot form: every matrix below is a product / regrouping of the NORMALISED matrices packed above, formed in fp64
+  void pack_slot_form() {
+    const int Hr = c.readout_mlp_width, H = c.latent_mlp_width, NG = b.ng0, SL1 = p.SL1;
+    put_slot(b.s_g0f, g0f);
+    put_slot(b.s_g0ft, transposed(g0f.data(), S, NG));
+    put_with_transpose(b.o_s_wk0, b.o_s_wt0, wenv0f, S, W);
+    // forward: first layers with the row blocks of the earlier latents folded; the tensor scalars' rows, transposed
     for (int l = 0; l < L; ++l) {
       const int K = S * (l + 1) + u;
-      const double* win = &h[p->latent[l].w[0]];  // [K, H]
+      const double* win = &h[b.latent[l].w[0]];  // [K, H]
       std::vector<double> f(win, win + size_t(K) * H);
-      for (int j = 0; j < l; ++j) {
-        fold_block(j, win, H, blk);
-        std::copy(blk.begin(), blk.end(), f.begin() + size_t(S) * (j + 1) * H);
-      }
-      put(p->s_in[l], f);
-      std::vector<double> sc(size_t(H) * u);
-      for (int k = 0; k < H; ++k)
-        for (int n = 0; n < u; ++n) sc[size_t(k) * u + n] = win[size_t(S * (l + 1) + n) * H + k];
-      put(p->s_sct[l], sc);
+      for (int j = 0; j < l; ++j) fold_rows(f, j, H);
+      put_slot(b.s_in[l], f);
+      put_slot(b.s_sct[l], transposed(win + size_t(S) * (l + 1) * H, u, H));
     }
-    const double* wro = &h[p->readout.w[0]];  // [SL1, Hr]
-    {
-      std::vector<double> f(wro, wro + size_t(SL1) * Hr);
-      for (int j = 0; j < L; ++j) {
-        fold_block(j, wro, Hr, blk);
-        std::copy(blk.begin(), blk.end(), f.begin() + size_t(S) * (j + 1) * Hr);
-      }
-      put(p->s_ro0, f);
-    }
+    const double* wro = &h[b.readout.w[0]];  // [SL1, Hr]
+    std::vector<double> ro0(wro, wro + size_t(SL1) * Hr);
+    for (int j = 0; j < L; ++j) fold_rows(ro0, j, Hr);
+    put_slot(b.s_ro0, ro0);
     // reverse, by slot: rows follow the operand [d readout hidden | d z_{l+1} .. d z_{L-1}], columns the hidden units of latent l
     for (int l = 0; l < L; ++l) {
-      std::vector<double> rs(size_t(Hr + S * (L - 1 - l)) * H);
-      fold_block(l, wro, Hr, blk);
-      for (int k = 0; k < Hr; ++k)
-        for (int m = 0; m < H; ++m) rs[size_t(k) * H + m] = blk[size_t(m) * Hr + k];
+      std::vector<double> rs = transposed(fold_block(l, wro, Hr).data(), H, Hr);
       for (int l2 = l + 1; l2 < L; ++l2) {
-        fold_block(l, &h[p->latent[l2].w[0]], H, blk);
-        for (int k = 0; k < H; ++k)
-          for (int m = 0; m < H; ++m) rs[size_t(Hr + S * (l2 - l - 1) + k) * H + m] = blk[size_t(m) * H + k];
+        const std::vector<double> t = transposed(fold_block(l, &h[b.latent[l2].w[0]], H).data(), H, H);
+        rs.insert(rs.end(), t.begin(), t.end());
       }
-      put(p->s_rs[l], rs);
+      put_slot(b.s_rs[l], rs);
     }
-    {
-      std::vector<double> tb(size_t(Hr + S * L) * S);
-      for (int k = 0; k < Hr; ++k)
-        for (int n = 0; n < S; ++n) tb[size_t(k) * S + n] = wro[size_t(n) * Hr + k];
-      for (int l2 = 0; l2 < L; ++l2)
-        for (int k = 0; k < H; ++k)
-          for (int n = 0; n < S; ++n) tb[size_t(Hr + S * l2 + k) * S + n] = h[p->latent[l2].w[0] + size_t(n) * H + k];
-      put(p->s_rstb, tb);
+    // ... and slot 0 (two-body): the two-body rows of the readout's and of every latent's first layer, transposed
+    std::vector<double> tb = transposed(wro, S, Hr);
+    for (int l2 = 0; l2 < L; ++l2) {
+      const std::vector<double> t = transposed(&h[b.latent[l2].w[0]], S, H);
+      tb.insert(tb.end(), t.begin(), t.end());
     }
+    put_slot(b.s_rstb, tb);
   }
-  struct SetRef { const GemmMatSet* m; };
-  std::vector<SetRef> proj_sets;
-  if (p->pipe.op_proj) {
+
+  // operator-kernel plans: per layer the R matrices f Wenv_l[:, r, :] [ka, u] and their transposes, f = 1 / sqrt(avg_num_neighbors)
+  void pack_proj_sets() {
     const double sf = 1.0 / std::sqrt(c.avg_num_neighbors);
     auto put_set = [&](const GemmMatSet& fw, const GemmMatSet& bw, size_t wk_off, int ka) {
-      for (int r = 0; r < Rr; ++r) {
+      for (int r = 0; r < R; ++r) {
         for (int k = 0; k < ka; ++k)
           for (int ch = 0; ch < u; ++ch) {
-            const double v = sf * h[wk_off + (size_t(k) * Rr + r) * u + ch];
+            const double v = sf * h[wk_off + (size_t(k) * R + r) * u + ch];
             h[fw.w + r * fw.w_bs + size_t(k) * u + ch] = v;
             h[bw.w + r * bw.w_bs + size_t(ch) * ka + k] = v;
           }
         gemm_pack_b(&h[fw.w + r * fw.w_bs], ka, u, &h[fw.wp + r * fw.wp_bs]);
         gemm_pack_b(&h[bw.w + r * bw.w_bs], u, ka, &h[bw.wp + r * bw.wp_bs]);
       }
-      proj_sets.push_back({&fw});
-      proj_sets.push_back({&bw});
+      proj_sets.push_back(&fw);
+      proj_sets.push_back(&bw);
     };
-    for (int l = 0; l < L; ++l) put_set(p->s_pr[l], p->s_prt[l], p->o_wk[l], l == 0 ? S : c.latent_mlp_width);
-    if (p->pipe.slot()) put_set(p->s_pr0f, p->s_prt0f, p->o_s_wk0, S);
+    for (int l = 0; l < L; ++l) put_set(b.s_pr[l], b.s_prt[l], b.o_wk[l], l == 0 ? S : c.latent_mlp_width);
+    if (pipe.slot()) put_set(b.s_pr0f, b.s_prt0f, b.o_s_wk0, S);
   }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (c.dtype == AA_F64) {
-    AA_CHECK_HIP(hipMemcpyAsync(dev_blob, h.data(), h.size() * 8, hipMemcpyHostToDevice, s));
-  } else {
-    std::vector<float> hf(h.begin(), h.end());
-    // bf16x3 copies are derived from the ROUNDED fp32 matrices (bit patterns stored in float slots)
+
+  // fp32 plans: round the blob once, then split the bf16x3 copies off the ROUNDED matrices (bit patterns stored in float slots)
+  void round_and_split(float* hf) {
+    for (size_t i = 0; i < b.n_elems; ++i) hf[i] = float(h[i]);
     auto splitw = [&](size_t w_off, int K, int N, size_t q_off) {
       gemm_pack_bf16x3(&hf[w_off], K, N, reinterpret_cast<unsigned*>(&hf[q_off]));
     };
@@ -1368,113 +1372,103 @@ extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_
         splitw(m.wt[i], m.dims[i + 1], m.dims[i], m.wtq[i]);
       }
     };
-    split_mlp(p->embed, c.embed_mlp_depth + 1);
-    splitw(p->o_g0, S, p->ng0, p->o_g0q);
-    splitw(p->o_g0t, p->ng0, S, p->o_g0tq);
-    for (int l = 0; l < L; ++l) split_mlp(p->latent[l], c.latent_mlp_depth + 1);
-    split_mlp(p->readout, c.readout_mlp_depth);
+    split_mlp(b.embed, c.embed_mlp_depth + 1);
+    splitw(b.o_g0, S, b.ng0, b.o_g0q);
+    splitw(b.o_g0t, b.ng0, S, b.o_g0tq);
+    for (int l = 0; l < L; ++l) split_mlp(b.latent[l], c.latent_mlp_depth + 1);
+    split_mlp(b.readout, c.readout_mlp_depth);
     for (const GemmMat* m : slot_mats) splitw(m->w, m->K, m->N, m->wq);
-    for (const SetRef& sr : proj_sets)
-      for (int r = 0; r < sr.m->count; ++r) splitw(sr.m->w + r * sr.m->w_bs, sr.m->K, sr.m->N, sr.m->wq + r * sr.m->wq_bs);
-    if (p->pipe.chains()) {
-      const int SL = S * L, SL1 = p->SL1, N2 = SL + c.num_tensor;
-      const float* rt = &hf[p->readout.wt[0]];          // [64, SL1]  (transposed first readout layer)
-      const float* lt = &hf[p->latent[L - 1].wt[0]];    // [64, N2]   (transposed first layer of the last latent)
-      // a: readout-reverse columns feeding the last latent; b: [readout-reverse ; latent-reverse] columns of the
-      // earlier features (d_fcat[:, :SL]); c: latent-reverse columns of the tensor scalars (d_scal)
-      std::vector<float> a(size_t(64) * S), b(size_t(128) * SL), cmat(size_t(64) * c.num_tensor);
-      for (int k = 0; k < 64; ++k) {
-        for (int n = 0; n < S; ++n) a[size_t(k) * S + n] = rt[size_t(k) * SL1 + SL + n];
-        for (int n = 0; n < SL; ++n) {
-          b[size_t(k) * SL + n] = rt[size_t(k) * SL1 + n];
-          b[size_t(64 + k) * SL + n] = lt[size_t(k) * N2 + n];
-        }
-        for (int n = 0; n < c.num_tensor; ++n) cmat[size_t(k) * c.num_tensor + n] = lt[size_t(k) * N2 + SL + n];
-      }
-      gemm_pack_bf16x3(a.data(), 64, S, reinterpret_cast<unsigned*>(&hf[p->o_b3a_q]));
-      gemm_pack_bf16x3(b.data(), 128, SL, reinterpret_cast<unsigned*>(&hf[p->o_b3b_q]));
-      gemm_pack_bf16x3(cmat.data(), 64, c.num_tensor, reinterpret_cast<unsigned*>(&hf[p->o_b3c_q]));
-    }
-    if (p->pipe.fold_embed_output) {
-      // (fold_embed_output) first stage behind the output layer of scalar_embed_mlp: W1 @ G0 and its transpose
-      const int NG = p->ng0;
-      std::vector<float> gf(size_t(64) * NG), gft(size_t(NG) * 64);
-      for (int k = 0; k < 64; ++k)
-        for (int q = 0; q < NG; ++q) {
-          double v = 0.0;
-          for (int m = 0; m < S; ++m) v += h[p->embed.w[1] + size_t(k) * S + m] * h[p->o_g0 + size_t(m) * NG + q];
-          gf[size_t(k) * NG + q] = float(v);
-          gft[size_t(q) * 64 + k] = float(v);
-        }
-      gemm_pack_bf16x3(gf.data(), 64, NG, reinterpret_cast<unsigned*>(&hf[p->o_g0fq]));
-      gemm_pack_bf16x3(gft.data(), NG, 64, reinterpret_cast<unsigned*>(&hf[p->o_g0tfq]));
-    }
-    if (p->pipe.fold_latent_outputs) {
-      // folded first layers (fold_latent_outputs): row block "lat_l" of a consumer's first layer <- Wout_l @ that block, in fp64 from the
-      // normalised matrices, rounded once.  Row order of the consumers: [two-body | lat0 | scal1] (latent 1), [two-body | lat0 | lat1] (readout)
-      const double* wo0 = &h[p->latent[0].w[1]];  // [64, 64] output layer of latent 0
-      const double* wo1 = &h[p->latent[1].w[1]];  // [64, 64] output layer of latent 1
-      auto folded = [&](const double* win, int K, const double* const* fold /* per 64-row block: Wout or nullptr */) {
-        std::vector<float> out(size_t(K) * 64);
-        for (int blk = 0; blk < K / 64; ++blk)
-          for (int r = 0; r < 64; ++r)
-            for (int n = 0; n < 64; ++n) {
-              double v = 0.0;
-              if (fold[blk]) {
-                for (int m = 0; m < 64; ++m) v += fold[blk][size_t(r) * 64 + m] * win[size_t(blk * 64 + m) * 64 + n];
-              } else {
-                v = win[size_t(blk * 64 + r) * 64 + n];
-              }
-              out[size_t(blk * 64 + r) * 64 + n] = float(v);
-            }
-        return out;
-      };
-      const double* f1[3] = {nullptr, wo0, nullptr};
-      const double* f2[3] = {nullptr, wo0, wo1};
-      const std::vector<float> l1 = folded(&h[p->latent[1].w[0]], 2 * S + c.num_tensor, f1);
-      const std::vector<float> r0 = folded(&h[p->readout.w[0]], 3 * S, f2);
-      gemm_pack_bf16x3(l1.data(), 2 * S + c.num_tensor, 64, reinterpret_cast<unsigned*>(&hf[p->o_lat1in_fq]));
-      gemm_pack_bf16x3(r0.data(), 3 * S, 64, reinterpret_cast<unsigned*>(&hf[p->o_ro0_fq]));
-      // readout-reverse chain: d a1 = d ro_h @ (Wout_1 @ Wro[lat1 rows])^T, one layer instead of two
-      std::vector<float> af(size_t(64) * 64);
-      for (int k = 0; k < 64; ++k)       // readout hidden unit
-        for (int m = 0; m < 64; ++m) {   // hidden unit of latent 1
-          double v = 0.0;
-          for (int n = 0; n < 64; ++n) v += wo1[size_t(m) * 64 + n] * h[p->readout.w[0] + size_t(2 * S + n) * 64 + k];
-          af[size_t(k) * 64 + m] = float(v);
-        }
-      gemm_pack_bf16x3(af.data(), 64, 64, reinterpret_cast<unsigned*>(&hf[p->o_b3af_q]));
-      // second layer of that chain, [readout' ; latent-1'] -> (d two-body | d lat0): with Wout_0^T folded into the lat0 columns it
-      // yields d a_0 (before the moments' share and silu'), and the latent-0 reverse chain needs no output-layer reverse
-      {
-        const int SL = S * L;
-        const float* rt = &hf[p->readout.wt[0]];
-        const float* lt = &hf[p->latent[L - 1].wt[0]];
-        const int N2 = SL + c.num_tensor, SL1_ = p->SL1;
-        if (p->pipe.fold_lat0_reverse) {
-        std::vector<double> b(size_t(128) * SL);
-        for (int k = 0; k < 64; ++k)
-          for (int n = 0; n < SL; ++n) {
-            b[size_t(k) * SL + n] = rt[size_t(k) * SL1_ + n];
-            b[size_t(64 + k) * SL + n] = lt[size_t(k) * N2 + n];
-          }
-        std::vector<float> bf(size_t(128) * SL);
-        for (int k = 0; k < 128; ++k)
-          for (int n = 0; n < SL; ++n) {
-            double v = b[size_t(k) * SL + n];
-            if (n >= S) {  // lat0 column block -> hidden unit m = n - S of latent 0
-              v = 0.0;
-              for (int q = 0; q < 64; ++q) v += b[size_t(k) * SL + S + q] * wo0[size_t(n - S) * 64 + q];
-            }
-            bf[size_t(k) * SL + n] = float(v);
-          }
-        gemm_pack_bf16x3(bf.data(), 128, SL, reinterpret_cast<unsigned*>(&hf[p->o_b3bf_q]));
-        }
-      }
-    }
-    AA_CHECK_HIP(hipMemcpyAsync(dev_blob, hf.data(), hf.size() * 4, hipMemcpyHostToDevice, s));
+    for (const GemmMatSet* m : proj_sets)
+      for (int r = 0; r < m->count; ++r) splitw(m->w + r * m->w_bs, m->K, m->N, m->wq + r * m->wq_bs);
   }
-  AA_CHECK_HIP(hipStreamSynchronize(s));  // host staging vectors die at return
+
+  // bf16x3 words of a [K, N] fp64 matrix, rounded to fp32 once
+  static void put_bf16x3(const std::vector<double>& m, int K, int N, float* hf, size_t q_off) {
+    const std::vector<float> f(m.begin(), m.end());
+    gemm_pack_bf16x3(f.data(), K, N, reinterpret_cast<unsigned*>(&hf[q_off]));
+  }
+
+  // Chains pipeline (fp32; S = u = every MLP width = 64): the merged reverse chain "readout' o latent_{L-1}'" (Runner::backward) and,
+  // 2-layer stacks, the bf16x3 copies of the folded layers.  The folds are formed in fp64 from the normalised matrices and rounded once.
+  void pack_chain_folds(float* hf) {
+    const int SL = S * L, SL1 = p.SL1, N2 = SL + u;
+    const float* rt = &hf[b.readout.wt[0]];        // [64, SL1]  (transposed first readout layer)
+    const float* lt = &hf[b.latent[L - 1].wt[0]];  // [64, N2]   (transposed first layer of the last latent)
+    // a: readout-reverse columns feeding the last latent; st: [readout-reverse ; latent-reverse] stacked, the columns of the
+    // earlier features (d_fcat[:, :SL]); cm: latent-reverse columns of the tensor scalars (d_scal)
+    std::vector<float> a(size_t(64) * S), st(size_t(128) * SL), cm(size_t(64) * u);
+    for (int k = 0; k < 64; ++k) {
+      for (int n = 0; n < S; ++n) a[size_t(k) * S + n] = rt[size_t(k) * SL1 + SL + n];
+      for (int n = 0; n < SL; ++n) {
+        st[size_t(k) * SL + n] = rt[size_t(k) * SL1 + n];
+        st[size_t(64 + k) * SL + n] = lt[size_t(k) * N2 + n];
+      }
+      for (int n = 0; n < u; ++n) cm[size_t(k) * u + n] = lt[size_t(k) * N2 + SL + n];
+    }
+    gemm_pack_bf16x3(a.data(), 64, S, reinterpret_cast<unsigned*>(&hf[b.o_b3a_q]));
+    gemm_pack_bf16x3(st.data(), 128, SL, reinterpret_cast<unsigned*>(&hf[b.o_b3b_q]));
+    gemm_pack_bf16x3(cm.data(), 64, u, reinterpret_cast<unsigned*>(&hf[b.o_b3c_q]));
+    if (pipe.fold_embed_output) {  // first stage behind the output layer of scalar_embed_mlp: W1 @ G0 and its transpose
+      put_bf16x3(g0f, 64, b.ng0, hf, b.o_g0fq);
+      put_bf16x3(transposed(g0f.data(), 64, b.ng0), b.ng0, 64, hf, b.o_g0tfq);
+    }
+    if (!pipe.fold_latent_outputs) return;
+    // folded first layers: row block "lat_l" of a consumer's first layer <- Wout_l @ that block.  Row order of the consumers:
+    // [two-body | lat0 | scal1] (latent 1), [two-body | lat0 | lat1] (readout)
+    const double* win1 = &h[b.latent[1].w[0]];
+    const double* wro = &h[b.readout.w[0]];
+    std::vector<double> l1(win1, win1 + size_t(2 * S + u) * 64), r0(wro, wro + size_t(3 * S) * 64);
+    fold_rows(l1, 0, 64);
+    fold_rows(r0, 0, 64);
+    fold_rows(r0, 1, 64);
+    put_bf16x3(l1, 2 * S + u, 64, hf, b.o_lat1in_fq);
+    put_bf16x3(r0, 3 * S, 64, hf, b.o_ro0_fq);
+    // readout-reverse chain: d a1 = d ro_h @ (Wout_1 @ Wro[lat1 rows])^T, one layer instead of two
+    put_bf16x3(transposed(&r0[size_t(2 * S) * 64], 64, 64), 64, 64, hf, b.o_b3af_q);
+    if (!pipe.fold_lat0_reverse) return;
+    // second layer of that chain, [readout' ; latent-1'] -> (d two-body | d lat0): with Wout_0^T folded into the lat0 columns it
+    // yields d a_0 (before the moments' share and silu'), and the latent-0 reverse chain needs no output-layer reverse
+    std::vector<double> stf(st.begin(), st.end());
+    const std::vector<double> lat0 = matmul(&stf[S], SL, &h[b.latent[0].wt[1]], 64, 128, 64, 64);  // [128, lat0 cols] @ Wout_0^T
+    for (int k = 0; k < 128; ++k) std::copy(&lat0[size_t(k) * 64], &lat0[size_t(k) * 64] + 64, &stf[size_t(k) * SL + S]);
+    put_bf16x3(stf, 128, SL, hf, b.o_b3bf_q);
+  }
+
+  // the blob as it will sit in device memory
+  int run(std::vector<unsigned char>& bytes) {
+    const bool f32 = c.dtype == AA_F32;
+    bytes.assign(b.n_elems * p.esize(), 0);
+    if (f32) stage.assign(b.n_elems, 0.0);
+    h = f32 ? stage.data() : reinterpret_cast<double*>(bytes.data());
+    if (int rc = pad_raw()) return rc;
+    if (int rc = pack_embedding()) return rc;
+    if (int rc = pack_mlps()) return rc;
+    if (pipe.fold_embed_output || pipe.slot()) fold_embed_output();
+    pack_embed_folds();
+    if (pipe.slot()) pack_slot_form();
+    if (pipe.op_proj) pack_proj_sets();
+    if (f32) {
+      float* hf = reinterpret_cast<float*>(bytes.data());
+      round_and_split(hf);
+      if (pipe.chains()) pack_chain_folds(hf);
+    }
+    return AA_OK;
+  }
+};
+
+static int pack_blob_host(const aa_model_plan& p, const aa_model_raw_weights& raw, std::vector<unsigned char>& bytes) {
+  return Packer{p, raw}.run(bytes);
+}
+
+extern "C" int aa_model_pack_weights(const aa_model_plan* p, const aa_model_raw_weights* raw, void* dev_blob, size_t blob_bytes,
+                                     aa_stream stream) {
+  AA_REQUIRE(p && raw && dev_blob, "aa_model_pack_weights: null argument");
+  AA_REQUIRE(blob_bytes >= aa_model_weights_bytes(p), "aa_model_pack_weights: blob too small");
+  std::vector<unsigned char> bytes;
+  if (int rc = pack_blob_host(*p, *raw, bytes)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  AA_CHECK_HIP(hipMemcpyAsync(dev_blob, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s));
+  AA_CHECK_HIP(hipStreamSynchronize(s));  // the host staging bytes die at return
   return AA_OK;
 }
 
@@ -1745,14 +1739,14 @@ struct Runner {
     a.l_max = c.l_max;
     a.S0 = c.embed_dim;
     a.poly_p = c.poly_p;
-    a.rmax_recip = wt(p->o_rmax);
-    a.bessel_w = wt(p->o_bessel);
-    a.center_embed = wt(p->o_cemb);
-    a.neighbor_embed = wt(p->o_nemb);
-    a.basis_w = wt(p->o_basis);
+    a.rmax_recip = wt(p->blob.o_rmax);
+    a.bessel_w = wt(p->blob.o_bessel);
+    a.center_embed = wt(p->blob.o_cemb);
+    a.neighbor_embed = wt(p->blob.o_nemb);
+    a.basis_w = wt(p->blob.o_basis);
     a.embed_kind = c.embed_kind;
     a.spline_span = c.spline_span;
-    a.emb_tab = p->pipe.two_body_table ? wt(p->o_embtab) : nullptr;
+    a.emb_tab = p->pipe.two_body_table ? wt(p->blob.o_embtab) : nullptr;
     a.vec = buf(w.vec);
     a.sh = buf(w.sh);
     a.emb0 = buf(w.emb0);
@@ -1778,11 +1772,11 @@ struct Runner {
       r.H = p->SL1;
       r.act = 0;
     }
-    r.w = wt(p->o_ro_last);
+    r.w = wt(p->blob.o_ro_last);
     r.act_kind = c.act_kind[2];
     r.factor = 1.0 / std::sqrt(2.0 * c.avg_num_neighbors);
-    r.scales = c.has_scales ? wt(p->o_scales) : nullptr;
-    r.shifts = c.has_shifts ? wt(p->o_shifts) : nullptr;
+    r.scales = c.has_scales ? wt(p->blob.o_scales) : nullptr;
+    r.shifts = c.has_shifts ? wt(p->blob.o_shifts) : nullptr;
     r.atom_energy = atom_energy;
     r.edge_sum = (p->pipe.chains() && atom_energy) ? buf(w.e_edge) : nullptr;  // written by the forward readout chain
     return r;
@@ -1807,8 +1801,8 @@ struct Runner {
     a.ld_we0 = p->W;
     a.wenv1 = buf(w.envw[1]);
     a.ld_we1 = p->W;
-    a.weights0 = wt(p->o_tpw[0]);
-    a.weights1 = wt(p->o_tpw[1]);
+    a.weights0 = wt(p->blob.o_tpw[0]);
+    a.weights1 = wt(p->blob.o_tpw[1]);
     a.coupling = c.tps[0].coupling;
     a.sf = 1.0 / std::sqrt(c.avg_num_neighbors);
     a.x2s0 = buf(w.x2s[0]);
@@ -1874,10 +1868,10 @@ struct Runner {
     m.a1 = buf(w.lat_h[0][c.latent_mlp_depth - 1]);
     m.ld_a1 = c.latent_mlp_width;
     m.ka1 = c.latent_mlp_width;
-    m.wk0 = wt(p->o_wk[0]);
-    m.wt0 = wt(p->o_wt[0]);
-    m.wk1 = wt(p->o_wk[1]);
-    m.wt1 = wt(p->o_wt[1]);
+    m.wk0 = wt(p->blob.o_wk[0]);
+    m.wt0 = wt(p->blob.o_wt[0]);
+    m.wk1 = wt(p->blob.o_wk[1]);
+    m.wt1 = wt(p->blob.o_wt[1]);
     m.waves_per_block = p->opt.moments_waves_per_block;
     return m;
   }
@@ -1898,7 +1892,7 @@ struct Runner {
     o.sf = 1.0 / std::sqrt(c.avg_num_neighbors);
     for (int m = 0; m < c.num_layers && m < 3; ++m) {
       o.x2s[m] = buf(w.x2s[m]);
-      o.tpw[m] = wt(p->o_tpw[m]);
+      o.tpw[m] = wt(p->blob.o_tpw[m]);
     }
     if (l == 0) {
       o.a = buf(w.emb);
@@ -1909,8 +1903,8 @@ struct Runner {
       o.ld_a = o.ka = c.latent_mlp_width;
       o.act = 1;
     }
-    o.wk = wt(p->o_wk[l]);
-    o.wt = wt(p->o_wt[l]);
+    o.wk = wt(p->blob.o_wk[l]);
+    o.wt = wt(p->blob.o_wt[l]);
     if (sp.slot) {
       // env inputs are hidden pre-activations everywhere: scalar_embed_mlp's (env weights behind its output layer) for layer 0,
       // slot l of the dense-net buffer (= z_{l-1}) afterwards
@@ -1918,8 +1912,8 @@ struct Runner {
         o.a = buf(w.se_h[c.embed_mlp_depth - 1]);
         o.ld_a = o.ka = c.embed_mlp_width;
         o.act = 1;
-        o.wk = wt(p->o_s_wk0);
-        o.wt = wt(p->o_s_wt0);
+        o.wk = wt(p->blob.o_s_wk0);
+        o.wt = wt(p->blob.o_s_wt0);
       } else {
         o.a = buf(w.fcat) + size_t(c.num_scalar) * l;
         o.ld_a = p->SL1;
@@ -1974,7 +1968,7 @@ struct Runner {
       o.proj_gemm = 1;
       if (int rc = launch_tp_op<T>(p->pipe.tp_op, l, false, o, stream, 1)) return rc;
       if (int rc = mark("tp_op_moments", p->D + o.ka)) return rc;
-      const GemmMatSet& ms = (l == 0 && sp.slot) ? p->s_pr0f : p->s_pr[l];
+      const GemmMatSet& ms = (l == 0 && sp.slot) ? p->blob.s_pr0f : p->blob.s_pr[l];
       if (int rc = proj_gemm(o, ms, buf(w.mom_op), int64_t(p->D) * o.ka, o.ka, buf(w.x2s[l]), int64_t(p->D) * u, u)) return rc;
       if (int rc = launch_tp_op<T>(p->pipe.tp_op, l, false, o, stream, 2)) return rc;
       return mark("tp_op_fwd", p->W + u, double(l + 1) * p->D * u);
@@ -2003,7 +1997,7 @@ struct Runner {
       o.dx2s = buf(w.dx2s_op);
       if (int rc = launch_tp_op<T>(p->pipe.tp_op, l, true, o, stream, 1)) return rc;
       if (int rc = mark("tp_op_bwd", elems - 2 * o.ka - p->D, double(L) * p->D * u)) return rc;
-      const GemmMatSet& ms = (l == 0 && sp.slot) ? p->s_prt0f : p->s_prt[l];
+      const GemmMatSet& ms = (l == 0 && sp.slot) ? p->blob.s_prt0f : p->blob.s_prt[l];
       if (int rc = proj_gemm(o, ms, buf(w.dx2s_op), int64_t(p->D) * u, u, buf(w.gm_op), int64_t(p->D) * o.ka, o.ka)) return rc;
       if (int rc = launch_tp_op<T>(p->pipe.tp_op, l, true, o, stream, 2)) return rc;
       return mark("tp_op_edge_env", 2 * o.ka + p->D);
@@ -2049,17 +2043,17 @@ struct Runner {
     a.embed_kind = c.embed_kind;
     a.spline_span = c.spline_span;
     a.poly_p = float(c.poly_p);
-    a.rmax_recip = wf(p->o_rmax);
-    a.bessel_w = wf(p->o_bessel);
-    a.emb_tab = wf(p->o_embtab_h);  // (folded: the table yields the first layer's pre-activation)
-    a.tpw0 = wf(p->o_tpw[0]);
-    a.tpw1 = wf(p->o_tpw[1]);
+    a.rmax_recip = wf(p->blob.o_rmax);
+    a.bessel_w = wf(p->blob.o_bessel);
+    a.emb_tab = wf(p->blob.o_embtab_h);  // (folded: the table yields the first layer's pre-activation)
+    a.tpw0 = wf(p->blob.o_tpw[0]);
+    a.tpw1 = wf(p->blob.o_tpw[1]);
     a.coupling = c.tps[0].coupling;
     a.sf = float(1.0 / std::sqrt(c.avg_num_neighbors));
-    a.ro_w = wf(p->o_ro_last);
+    a.ro_w = wf(p->blob.o_ro_last);
     a.ro_factor = float(1.0 / std::sqrt(2.0 * c.avg_num_neighbors));
-    a.scales = c.has_scales ? wf(p->o_scales) : nullptr;
-    a.shifts = c.has_shifts ? wf(p->o_shifts) : nullptr;
+    a.scales = c.has_scales ? wf(p->blob.o_scales) : nullptr;
+    a.shifts = c.has_shifts ? wf(p->blob.o_shifts) : nullptr;
     a.vec = bf(w.vec);
     a.sh = bf(w.sh);
     a.se_h = bf(w.se_h[0]);
@@ -2105,12 +2099,12 @@ struct Runner {
   // fold_embed_table, fold_embed_output, fold_latent_outputs)
   int fused_program_one_wave(FusedFwdArgs& a) const {
     FusedProgram prog{a, p->R};
-    prog.env(wf(p->o_wk0f));
-    prog.layer(wf(p->o_g0fq), 2, 0, 2 + 2 * p->R);
-    prog.layer(wf(p->latent[0].wq[0]), 4, 0, 2);
-    prog.env(wf(p->o_wk[1]));
-    prog.layer(wf(p->o_lat1in_fq), 6, 0, 2);
-    prog.layer(wf(p->o_ro0_fq), 6, 0, 2);
+    prog.env(wf(p->blob.o_wk0f));
+    prog.layer(wf(p->blob.o_g0fq), 2, 0, 2 + 2 * p->R);
+    prog.layer(wf(p->blob.latent[0].wq[0]), 4, 0, 2);
+    prog.env(wf(p->blob.o_wk[1]));
+    prog.layer(wf(p->blob.o_lat1in_fq), 6, 0, 2);
+    prog.layer(wf(p->blob.o_ro0_fq), 6, 0, 2);
     if (prog.ns != fused_fwd_num_steps(p->R) || prog.ns > kFusedMaxSteps) return fail(AA_ERR_INVALID, "fused forward: program length mismatch");
     return AA_OK;
   }
@@ -2120,22 +2114,22 @@ struct Runner {
   // chain [| deep tail]] -- and what the tail writes
   int fused_program_wide(FusedFwdArgs& a8, ReverseInForward tail) const {
     FusedProgram prog{a8, p->R};
-    prog.env(wf(p->o_wk0f));
-    prog.layer(wf(p->o_g0fq), 2, 0, 2 + 2 * p->R);
-    prog.layer(wf(p->latent[0].wq[0]), 4, 0, 2);
-    prog.env(wf(p->o_wk[1]));
-    prog.chunk(wf(p->o_lat1in_fq), 6, 4);
-    prog.chunk(wf(p->o_lat1in_fq), 6, 5);
+    prog.env(wf(p->blob.o_wk0f));
+    prog.layer(wf(p->blob.o_g0fq), 2, 0, 2 + 2 * p->R);
+    prog.layer(wf(p->blob.latent[0].wq[0]), 4, 0, 2);
+    prog.env(wf(p->blob.o_wk[1]));
+    prog.chunk(wf(p->blob.o_lat1in_fq), 6, 4);
+    prog.chunk(wf(p->blob.o_lat1in_fq), 6, 5);
     for (int kc : {2, 3, 0, 1}) {
-      prog.chunk(wf(p->o_lat1in_fq), 6, kc);
-      prog.chunk(wf(p->o_ro0_fq), 6, kc);
+      prog.chunk(wf(p->blob.o_lat1in_fq), 6, kc);
+      prog.chunk(wf(p->blob.o_ro0_fq), 6, kc);
     }
-    prog.chunk(wf(p->o_ro0_fq), 6, 4);
-    prog.chunk(wf(p->o_ro0_fq), 6, 5);
+    prog.chunk(wf(p->blob.o_ro0_fq), 6, 4);
+    prog.chunk(wf(p->blob.o_ro0_fq), 6, 5);
     if (tail != ReverseInForward::None) {
-      prog.layer(wf(p->o_b3af_q), 2, 0, 2);
-      prog.layer(wf(p->pipe.fold_lat0_reverse ? p->o_b3bf_q : p->o_b3b_q), 4, 0, 4);
-      prog.layer(wf(p->o_b3c_q), 2, 0, 2);
+      prog.layer(wf(p->blob.o_b3af_q), 2, 0, 2);
+      prog.layer(wf(p->pipe.fold_lat0_reverse ? p->blob.o_b3bf_q : p->blob.o_b3b_q), 4, 0, 4);
+      prog.layer(wf(p->blob.o_b3c_q), 2, 0, 2);
       a8.g_fcat = bf(w.g_fcat);
       a8.ld_gfcat = p->SL1;
       a8.g_scal1 = bf(w.g_scal[1]);
@@ -2144,8 +2138,8 @@ struct Runner {
       // + the transposed layer-1 env weights [R][u][64] as they are packed for tp_mom_bwd_last -- four windows of 48 of their
       //   64 R rows, the last one(s) pulled back inside the matrix (fused_fwd8_kernel: project_moments_t) -- and the first
       //   layer of latent 0, transposed (the resident chain's bytes)
-      for (int cblk = 0; cblk < 4; ++cblk) prog.rows(wf(p->o_wt[1]) + size_t(std::min(48 * cblk, 64 * p->R - 48)) * 64);
-      prog.layer(wf(p->latent[0].wtq[0]), 2, 0, 4);
+      for (int cblk = 0; cblk < 4; ++cblk) prog.rows(wf(p->blob.o_wt[1]) + size_t(std::min(48 * cblk, 64 * p->R - 48)) * 64);
+      prog.layer(wf(p->blob.latent[0].wtq[0]), 2, 0, 4);
       a8.g_scal0 = bf(w.g_scal[0]);
       a8.gsh_env1 = bf(w.g_sh) + size_t(2) * size_t(E) * p->D;
     }
@@ -2159,7 +2153,7 @@ struct Runner {
     const int S = p->cfg.num_scalar, u = p->cfg.num_tensor;
     double per_edge = 1 + (g->shift_vec ? 3 : 0) + 3 + 4 + p->D + 5 * 64 + p->W;
     const double per_atom = 3 + 2.0 * p->D * u + 1 + 1;
-    double fl = 2.0 * double(E) * (2.0 * 64 * 64 + 64.0 * p->ng0 + double(S + u) * 64 + 64.0 * S + double(2 * S + u) * 64 + 64.0 * S + 3.0 * S * 64);
+    double fl = 2.0 * double(E) * (2.0 * 64 * 64 + 64.0 * p->blob.ng0 + double(S + u) * 64 + 64.0 * S + double(2 * S + u) * 64 + 64.0 * S + 3.0 * S * 64);
     if (sp.reverse_in_forward != ReverseInForward::None) {  // (+ the readout-reverse chain: 192 gradient columns out instead of two 64-wide pre-activation rows)
       fl += 2.0 * double(E) * (64.0 * 64 + 128.0 * 128 + 64.0 * 64);
       per_edge += 64;
@@ -2205,17 +2199,17 @@ struct Runner {
       SegList c0{1, {seg(buf(w.se_h[0]), 64, 64)}};
       SegList c1{1, {seg(buf(w.emb), S, S)}};
       SegList c2{2, {seg(buf(w.fcat), SL1, S), seg(buf(w.w0), W, W)}};
-      ca.L[0] = chain_layer(E, in, 0, wt(p->embed.wq[0]), c.embed_dim, 64, c0, nullptr, nullptr, nullptr, 0, 0, 1);
+      ca.L[0] = chain_layer(E, in, 0, wt(p->blob.embed.wq[0]), c.embed_dim, 64, c0, nullptr, nullptr, nullptr, 0, 0, 1);
       if (sp.forward == ForwardKind::StagedFolded) {
         // folded: a_e = silu(h_e) is stored where the embedding used to be; [two_body | w0] = a_e @ (W1 G0)
         ca.nlayers = 2;
         ca.L[0].kept_out = buf(w.emb);
         ca.L[0].ld_kept = S;
-        ca.L[1] = chain_layer(E, none, 0, wt(p->o_g0fq), 64, p->ng0, c2, nullptr, nullptr, nullptr, 1, -1, 0);
+        ca.L[1] = chain_layer(E, none, 0, wt(p->blob.o_g0fq), 64, p->blob.ng0, c2, nullptr, nullptr, nullptr, 1, -1, 0);
       } else {
         ca.nlayers = 3;
-        ca.L[1] = chain_layer(E, none, 0, wt(p->embed.wq[1]), 64, S, c1, nullptr, nullptr, nullptr, 1, 0, 0);
-        ca.L[2] = chain_layer(E, none, 0, wt(p->o_g0q), 64, p->ng0, c2, nullptr, nullptr, nullptr, 1, -1, 0);
+        ca.L[1] = chain_layer(E, none, 0, wt(p->blob.embed.wq[1]), 64, S, c1, nullptr, nullptr, nullptr, 1, 0, 0);
+        ca.L[2] = chain_layer(E, none, 0, wt(p->blob.o_g0q), 64, p->blob.ng0, c2, nullptr, nullptr, nullptr, 1, -1, 0);
       }
       return run_chain(ca, "F1");
     }
@@ -2223,17 +2217,17 @@ struct Runner {
       // 3: hidden layers of scalar_embed_mlp; 4 + 5a on the activated last hidden layer (output layer folded into G0)
       const int De = c.embed_mlp_depth, He = c.embed_mlp_width;
       SegList hid{1, {seg(buf(w.se_h[De - 1]), He, He)}};
-      if (int rc = mlp_fwd(p->embed, De, in, w.se_h, hid, 0)) return rc;
+      if (int rc = mlp_fwd(p->blob.embed, De, in, w.se_h, hid, 0)) return rc;
       SegList out{2, {seg(buf(w.fcat), SL1, S), seg(buf(w.w0), W, W)}};
       act_now = c.act_kind[0];
-      return gemm(hid, 1, p->s_g0f, out);
+      return gemm(hid, 1, p->blob.s_g0f, out);
     }
     SegList emb{1, {seg(buf(w.emb), S, S)}};
-    if (int rc = mlp_fwd(p->embed, c.embed_mlp_depth + 1, in, w.se_h, emb, 0)) return rc;
+    if (int rc = mlp_fwd(p->blob.embed, c.embed_mlp_depth + 1, in, w.se_h, emb, 0)) return rc;
     SegList out{3, {seg(buf(w.fcat), SL1, S), seg(buf(w.w0), W, W), seg(buf(w.envw[0]), W, W)}};
     if (p->pipe.env_moments()) out.count = 2;
     act_now = AA_ACT_SILU;  // (a plain linear map: no activation involved)
-    return gemm(emb, 0, wt(p->o_g0), wt(p->o_g0p), wt(p->o_g0q), S, p->ng0, out, nullptr, nullptr);
+    return gemm(emb, 0, wt(p->blob.o_g0), wt(p->blob.o_g0p), wt(p->blob.o_g0q), S, p->blob.ng0, out, nullptr, nullptr);
   }
 
   // operands both directions of a tensor-product layer take, per-edge kernels with compile-time tables (TpPath::Spec, SpecChain) ...
@@ -2253,7 +2247,7 @@ struct Runner {
     }
     a.w_env = buf(w.envw[l]);
     a.ld_we = p->W;
-    a.weights = wt(p->o_tpw[l]);
+    a.weights = wt(p->blob.o_tpw[l]);
     a.coupling = p->cfg.tps[l].coupling;
     a.sf = 1.0 / std::sqrt(p->cfg.avg_num_neighbors);
     a.x2s = buf(w.x2s[l]);
@@ -2269,7 +2263,7 @@ struct Runner {
     else
       a.x1.dense = buf(w.tf[l - 1]);
     a.x2 = implicit(w.envw[l]);
-    a.weights = wt(p->o_tpw[l]);
+    a.weights = wt(p->blob.o_tpw[l]);
     a.scatter_factor = 1.0 / std::sqrt(p->cfg.avg_num_neighbors);
     a.x2s = buf(w.x2s[l]);
   }
@@ -2284,7 +2278,7 @@ struct Runner {
         TpMomArgs m = mom_args(g);
         if (l == 0) {
           m.c.scal1 = buf(w.scal[0]);  // the first-layer kernel writes its scalars through this field
-          if (sp.forward == ForwardKind::StagedFolded) m.wk0 = wt(p->o_wk0f);  // (its env input is a_e: env weights behind the output layer of scalar_embed_mlp)
+          if (sp.forward == ForwardKind::StagedFolded) m.wk0 = wt(p->blob.o_wk0f);  // (its env input is a_e: env weights behind the output layer of scalar_embed_mlp)
           if (int rc = launch_tp_mom_fwd_first<T>(p->pipe.chain_pair, m, stream)) return rc;
           return mark("tp_mom_fwd_first", p->D + m.ka0 + W + u, double(p->D) * u);
         }
@@ -2332,7 +2326,7 @@ struct Runner {
       SegList cl{1, {seg(buf(w.fcat) + S * (l + 1), SL1, S)}};
       SegList fin{1, {seg(buf(w.fcat), SL1, S * L)}};
       SegList cr{1, {seg(buf(w.ro_h[0]), 64, 64)}};
-      ca.L[0] = chain_layer(E, in, 0, wt(p->latent[l].wq[0]), S * (l + 1) + u, 64, ch, nullptr, nullptr, nullptr, 0, 0, 1);
+      ca.L[0] = chain_layer(E, in, 0, wt(p->blob.latent[l].wq[0]), S * (l + 1) + u, 64, ch, nullptr, nullptr, nullptr, 0, 0, 1);
       if (folded && l < L - 1) {
         // folded: no output layer; a_l = silu(z_l) goes where lat_l used to be
         ca.nlayers = 1;
@@ -2341,20 +2335,20 @@ struct Runner {
       } else if (folded) {
         // folded: latent 1 and the readout on [two-body | a_0 | ...] with the output layers folded into their row blocks; a_1 stays in registers
         ca.nlayers = 2;
-        ca.L[0] = chain_layer(E, in, 0, wt(p->o_lat1in_fq), S * (l + 1) + u, 64, ch, nullptr, nullptr, nullptr, 0, 0, 1);
-        ca.L[1] = chain_layer(E, fin, 0, wt(p->o_ro0_fq), S * L + 64, 64, cr, nullptr, nullptr, nullptr, 1, -1, 0);
+        ca.L[0] = chain_layer(E, in, 0, wt(p->blob.o_lat1in_fq), S * (l + 1) + u, 64, ch, nullptr, nullptr, nullptr, 0, 0, 1);
+        ca.L[1] = chain_layer(E, fin, 0, wt(p->blob.o_ro0_fq), S * L + 64, 64, cr, nullptr, nullptr, nullptr, 1, -1, 0);
         ca.L[1].edge_sum_out = buf(w.e_edge);
-        ca.ro_w = wt(p->o_ro_last);
+        ca.ro_w = wt(p->blob.o_ro_last);
       } else if (l < L - 1) {
         ca.nlayers = 2;
-        ca.L[1] = chain_layer(E, none, 0, wt(p->latent[l].wq[1]), 64, S, cl, nullptr, nullptr, nullptr, 1, -1, 0);
+        ca.L[1] = chain_layer(E, none, 0, wt(p->blob.latent[l].wq[1]), 64, S, cl, nullptr, nullptr, nullptr, 1, -1, 0);
       } else {
         // last latent + the readout's GEMM layer: lat_{L-1} stays in registers as the tail of the readout input
         ca.nlayers = 3;
-        ca.L[1] = chain_layer(E, none, 0, wt(p->latent[l].wq[1]), 64, S, cl, nullptr, nullptr, nullptr, 1, 0, 0);
-        ca.L[2] = chain_layer(E, fin, 0, wt(p->readout.wq[0]), S * L + 64, 64, cr, nullptr, nullptr, nullptr, 1, -1, 0);
+        ca.L[1] = chain_layer(E, none, 0, wt(p->blob.latent[l].wq[1]), 64, S, cl, nullptr, nullptr, nullptr, 1, 0, 0);
+        ca.L[2] = chain_layer(E, fin, 0, wt(p->blob.readout.wq[0]), S * L + 64, 64, cr, nullptr, nullptr, nullptr, 1, -1, 0);
         ca.L[2].edge_sum_out = buf(w.e_edge);  // last linear readout layer folded into the epilogue
-        ca.ro_w = wt(p->o_ro_last);
+        ca.ro_w = wt(p->blob.o_ro_last);
       }
       return run_chain(ca, "F2");
     }
@@ -2363,13 +2357,13 @@ struct Runner {
       // folded into this layer's row blocks)
       SegList zl{1, {seg(buf(w.fcat) + S * (l + 1), SL1, S)}};
       act_now = c.act_kind[1];
-      return gemm(in, l > 0, p->s_in[l], zl, nullptr, nullptr, S, S * (l + 1));
+      return gemm(in, l > 0, p->blob.s_in[l], zl, nullptr, nullptr, S, S * (l + 1));
     }
     SegList out;
     out.count = (l < L - 1 && !p->pipe.env_moments()) ? 2 : 1;
     out.s[0] = seg(buf(w.fcat) + S * (l + 1), SL1, S);
     if (l < L - 1 && !p->pipe.env_moments()) out.s[1] = seg(buf(w.envw[l + 1]), W, W);
-    return mlp_fwd(p->latent[l], c.latent_mlp_depth + 1, in, w.lat_h[l], out, 1);
+    return mlp_fwd(p->blob.latent[l], c.latent_mlp_depth + 1, in, w.lat_h[l], out, 1);
   }
 
   // 6: edge readout GEMM layers (the chains ran theirs behind the last latent), 7-8: last linear + edge sum + per-type scale/shift
@@ -2383,9 +2377,9 @@ struct Runner {
         SegList cs{1, {seg(buf(w.ro_h[i]), c.readout_mlp_width, c.readout_mlp_width)}};
         if (sp.slot && i == 0) {
           act_now = c.act_kind[1];  // (the activated columns are the latents' hidden layers)
-          if (int rc = gemm(a, 1, p->s_ro0, cs, nullptr, nullptr, S, SL1)) return rc;
+          if (int rc = gemm(a, 1, p->blob.s_ro0, cs, nullptr, nullptr, S, SL1)) return rc;
           act_now = c.act_kind[2];
-        } else if (int rc = gemm(a, i > 0, wt(p->readout.w[i]), wt(p->readout.wp[i]), wt(p->readout.wq[i]), p->readout.dims[i], p->readout.dims[i + 1], cs,
+        } else if (int rc = gemm(a, i > 0, wt(p->blob.readout.w[i]), wt(p->blob.readout.wp[i]), wt(p->blob.readout.wq[i]), p->blob.readout.dims[i], p->blob.readout.dims[i + 1], cs,
                                  nullptr, nullptr)) {
           return rc;
         }
@@ -2420,7 +2414,7 @@ struct Runner {
     a.pos = pos;
     a.shift_vec = g->shift_vec;
     a.num_types = p->cfg.num_types;
-    a.rmax_recip = wt(p->o_rmax);
+    a.rmax_recip = wt(p->blob.o_rmax);
     a.tab = p->zbl_tab;
     a.poly_p = p->zbl_poly_p;
     a.atom_energy = e_out;
@@ -2479,7 +2473,7 @@ struct Runner {
         SegList a{1, {seg(buf(w.g_ro_h[i]), Hr, Hr)}};
         SegList cs{1, {seg(buf(w.g_ro_h[i - 1]), Hr, Hr)}};
         SegList z{1, {seg(buf(w.ro_h[i - 1]), Hr, Hr)}};
-        if (int rc = gemm(a, 0, wt(p->readout.wt[i]), wt(p->readout.wtp[i]), wt(p->readout.wtq[i]), p->readout.dims[i + 1], p->readout.dims[i], cs, nullptr, &z))
+        if (int rc = gemm(a, 0, wt(p->blob.readout.wt[i]), wt(p->blob.readout.wtp[i]), wt(p->blob.readout.wtq[i]), p->blob.readout.dims[i + 1], p->blob.readout.dims[i], cs, nullptr, &z))
           return rc;
       }
     }
@@ -2490,9 +2484,9 @@ struct Runner {
       SegList z{1, {seg(buf(w.fcat) + S * (l + 1), SL1, S)}};
       SegList ad{1, {seg(buf(w.g_aenv), H, H)}};
       act_now = c.act_kind[1];
-      if (int rc = gemm(a, 0, p->s_rs[l], dz, &z, l < L - 1 ? &ad : nullptr)) return rc;
+      if (int rc = gemm(a, 0, p->blob.s_rs[l], dz, &z, l < L - 1 ? &ad : nullptr)) return rc;
       SegList gs{1, {seg(buf(w.g_scal[l]), u, u)}};
-      if (int rc = gemm(dz, 0, p->s_sct[l], gs)) return rc;
+      if (int rc = gemm(dz, 0, p->blob.s_sct[l], gs)) return rc;
       // tensor-product layer reverse (per-atom operator kernels)
       if (int rc = run_op_bwd(g, l)) return rc;
     }
@@ -2500,7 +2494,7 @@ struct Runner {
     {
       SegList a{2, {seg(buf(w.g_ro_h[0]), Hr, Hr), seg(buf(w.g_fcat) + S, SL1, S * L)}};
       SegList tb{1, {seg(buf(w.g_fcat), SL1, S)}};
-      if (int rc = gemm(a, 0, p->s_rstb, tb)) return rc;
+      if (int rc = gemm(a, 0, p->blob.s_rstb, tb)) return rc;
     }
     // first stage + output layer of scalar_embed_mlp: d h = ([d two-body | d w0] @ (W_last G0)^T + d a_e of the moments) * act'(h)
     {
@@ -2509,9 +2503,9 @@ struct Runner {
       SegList z{1, {seg(buf(w.se_h[De - 1]), He, He)}};
       SegList ad{1, {seg(buf(w.g_aenv), He, He)}};
       act_now = c.act_kind[0];
-      if (int rc = gemm(a, 0, p->s_g0ft, dh, &z, &ad)) return rc;
+      if (int rc = gemm(a, 0, p->blob.s_g0ft, dh, &z, &ad)) return rc;
       SegList gi{1, {seg(buf(w.g_emb0), c.embed_dim, c.embed_dim)}};
-      if (int rc = mlp_bwd(p->embed, De, dh, w.se_h, w.g_se_h, gi, nullptr, 0)) return rc;
+      if (int rc = mlp_bwd(p->blob.embed, De, dh, w.se_h, w.g_se_h, gi, nullptr, 0)) return rc;
     }
     return edge_tail(g, pos, forces);
   }
@@ -2554,19 +2548,19 @@ struct Runner {
       if (p->pipe.fold_latent_outputs && L == 2) {
         // "d lat1 = d ro_h @ Wro[lat1]^T" and "d a1 = d lat1 @ Wout_1^T" as ONE 64x64 layer (folded at pack time): 12 instead of 14 steps
         ca.nlayers = 3;
-        ca.L[0] = chain_layer(E, in, 0, wt(p->o_b3af_q), 64, 64, cn, nullptr, &z1, nullptr, 0, 0, 0);
+        ca.L[0] = chain_layer(E, in, 0, wt(p->blob.o_b3af_q), 64, 64, cn, nullptr, &z1, nullptr, 0, 0, 0);
         ca.L[0].a_mode = 1;
-        ca.L[1] = chain_layer(E, in, 0, wt(p->pipe.fold_lat0_reverse ? p->o_b3bf_q : p->o_b3b_q), 128, S * L, c2, nullptr, nullptr, nullptr, 1, -1, 0);
+        ca.L[1] = chain_layer(E, in, 0, wt(p->pipe.fold_lat0_reverse ? p->blob.o_b3bf_q : p->blob.o_b3b_q), 128, S * L, c2, nullptr, nullptr, nullptr, 1, -1, 0);
         ca.L[1].a_mode = 1;
-        ca.L[2] = chain_layer(E, none, 0, wt(p->o_b3c_q), 64, u, c3, nullptr, nullptr, nullptr, 1, -1, 0);
+        ca.L[2] = chain_layer(E, none, 0, wt(p->blob.o_b3c_q), 64, u, c3, nullptr, nullptr, nullptr, 1, -1, 0);
       } else {
         ca.nlayers = 4;
-        ca.L[0] = chain_layer(E, in, 0, wt(p->o_b3a_q), 64, S, cn, nullptr, nullptr, nullptr, 0, 0, 0);
+        ca.L[0] = chain_layer(E, in, 0, wt(p->blob.o_b3a_q), 64, S, cn, nullptr, nullptr, nullptr, 0, 0, 0);
         ca.L[0].a_mode = 1;
-        ca.L[1] = chain_layer(E, none, 0, wt(p->latent[L - 1].wtq[1]), S, 64, cn, nullptr, &z1, nullptr, 1, 0, 0);
-        ca.L[2] = chain_layer(E, in, 0, wt(p->o_b3b_q), 128, S * L, c2, nullptr, nullptr, nullptr, 1, -1, 0);
+        ca.L[1] = chain_layer(E, none, 0, wt(p->blob.latent[L - 1].wtq[1]), S, 64, cn, nullptr, &z1, nullptr, 1, 0, 0);
+        ca.L[2] = chain_layer(E, in, 0, wt(p->blob.o_b3b_q), 128, S * L, c2, nullptr, nullptr, nullptr, 1, -1, 0);
         ca.L[2].a_mode = 1;
-        ca.L[3] = chain_layer(E, none, 0, wt(p->o_b3c_q), 64, u, c3, nullptr, nullptr, nullptr, 1, -1, 0);
+        ca.L[3] = chain_layer(E, none, 0, wt(p->blob.o_b3c_q), 64, u, c3, nullptr, nullptr, nullptr, 1, -1, 0);
       }
       return run_chain(ca, "B3");
     }
@@ -2593,7 +2587,7 @@ struct Runner {
       } else {
         cs = SegList{1, {seg(buf(w.g_fcat), SL1, SL1)}};
       }
-      if (int rc = gemm(a, 0, wt(p->readout.wt[i]), wt(p->readout.wtp[i]), wt(p->readout.wtq[i]), p->readout.dims[i + 1], p->readout.dims[i], cs,
+      if (int rc = gemm(a, 0, wt(p->blob.readout.wt[i]), wt(p->blob.readout.wtp[i]), wt(p->blob.readout.wtq[i]), p->blob.readout.dims[i + 1], p->blob.readout.dims[i], cs,
                         nullptr, zp))
         return rc;
       a = cs;
@@ -2619,7 +2613,7 @@ struct Runner {
         if (l < L - 1 && !p->pipe.env_moments()) go.s[1] = seg(buf(w.g_envw), W, W);
         SegList aenv{1, {seg(p->pipe.env_moments() ? buf(w.g_aenv) : nullptr, c.latent_mlp_width, c.latent_mlp_width)}};
         const SegList* addp = (p->pipe.env_moments() && l < L - 1) ? &aenv : nullptr;
-        return mlp_bwd(p->latent[l], c.latent_mlp_depth + 1, go, w.lat_h[l], w.g_lat_h, c1, acc1, 1, addp);
+        return mlp_bwd(p->blob.latent[l], c.latent_mlp_depth + 1, go, w.lat_h[l], w.g_lat_h, c1, acc1, 1, addp);
       }
       case LatentReverse::InForwardTail:  // (ran in the deep tail of the fused forward)
         return AA_OK;
@@ -2628,8 +2622,8 @@ struct Runner {
         SegList cn{1, {seg(nullptr, 64, 64)}};
         SegList zz{1, {seg(buf(w.lat_h[l][0]), 64, 64)}};
         SegList ad{1, {seg(buf(w.g_aenv), 64, 64)}};
-        ca.L[0] = chain_layer(E, in, 0, wt(p->latent[l].wtq[1]), S, 64, cn, nullptr, &zz, &ad, 0, 0, 0);
-        ca.L[1] = chain_layer(E, none, 0, wt(p->latent[l].wtq[0]), 64, S * (l + 1) + u, c1, acc1, nullptr, nullptr, 1, -1, 0);
+        ca.L[0] = chain_layer(E, in, 0, wt(p->blob.latent[l].wtq[1]), S, 64, cn, nullptr, &zz, &ad, 0, 0, 0);
+        ca.L[1] = chain_layer(E, none, 0, wt(p->blob.latent[l].wtq[0]), 64, S * (l + 1) + u, c1, acc1, nullptr, nullptr, 1, -1, 0);
         return run_chain(ca, "B2");
       }
       case LatentReverse::FoldedChain:
@@ -2638,7 +2632,7 @@ struct Runner {
         // reverse is elementwise -- d h = (d a_0 + d a_0 of the moments) x silu'(h) -- and rides as the operand transform of the
         // first-layer reverse: ONE layer, 4 steps instead of 6
         ca.nlayers = 1;
-        ca.L[0] = chain_layer(E, in, 0, wt(p->latent[l].wtq[0]), 64, S * (l + 1) + u, c1, acc1, nullptr, nullptr, 0, -1, 0);
+        ca.L[0] = chain_layer(E, in, 0, wt(p->blob.latent[l].wtq[0]), 64, S * (l + 1) + u, c1, acc1, nullptr, nullptr, 0, -1, 0);
         ca.L[0].a_mode = 2;
         ca.L[0].a2_add = buf(w.g_aenv);
         ca.L[0].ld_a2add = 64;
@@ -2656,7 +2650,7 @@ struct Runner {
           b2.ldadd = 64;
           b2.z = reinterpret_cast<const float*>(buf(w.lat_h[l][0]));
           b2.ldz = 64;
-          b2.Wq = wt(p->latent[l].wtq[0]);
+          b2.Wq = wt(p->blob.latent[l].wtq[0]);
           b2.c0 = reinterpret_cast<float*>(buf(w.g_fcat));
           b2.ldc0 = SL1;
           b2.c1 = reinterpret_cast<float*>(buf(w.g_scal[l]));
@@ -2693,7 +2687,7 @@ struct Runner {
         m.ld_ga = S;
         // (after a fused forward the embedding's slot holds a_e = silu(h) of scalar_embed_mlp and the env weights are folded behind
         //  its output layer, fold_embed_output: d a_e comes out instead of d emb)
-        if (sp.folded_first_stage()) m.wt0 = wt(p->o_wt0f);
+        if (sp.folded_first_stage()) m.wt0 = wt(p->blob.o_wt0f);
         if (int rc = launch_tp_mom_bwd_first<T>(p->pipe.chain_pair, m, stream)) return rc;
         return mark("tp_mom_bwd_first", p->D + 2 * W + 2 * u + 2 * m.ka0 + 2 * p->D, 2.0 * p->D * u);
       }
@@ -2769,14 +2763,14 @@ struct Runner {
         SegList gi{1, {seg(buf(w.g_emb), S, S)}};
         SegList aenv{1, {seg(p->pipe.env_moments() ? buf(w.g_aenv) : nullptr, S, S)}};
         act_now = AA_ACT_SILU;
-        if (int rc = gemm(go, 0, wt(p->o_g0t), wt(p->o_g0tp), wt(p->o_g0tq), p->ng0, S, gi, nullptr, nullptr,
+        if (int rc = gemm(go, 0, wt(p->blob.o_g0t), wt(p->blob.o_g0tp), wt(p->blob.o_g0tq), p->blob.ng0, S, gi, nullptr, nullptr,
                           p->pipe.env_moments() ? &aenv : nullptr))
           return rc;
       }
       // scalar_embed_mlp reverse
       SegList go{1, {seg(buf(w.g_emb), S, S)}};
       SegList gi{1, {seg(buf(w.g_emb0), c.embed_dim, c.embed_dim)}};
-      return mlp_bwd(p->embed, c.embed_mlp_depth + 1, go, w.se_h, w.g_se_h, gi, nullptr, 0);
+      return mlp_bwd(p->blob.embed, c.embed_mlp_depth + 1, go, w.se_h, w.g_se_h, gi, nullptr, 0);
     }
     // ... in ONE kernel
     const SegList none{0, {}};
@@ -2787,9 +2781,9 @@ struct Runner {
     SegList ad{1, {seg(buf(w.g_aenv), S, S)}};
     SegList zz{1, {seg(buf(w.se_h[0]), 64, 64)}};
     SegList ce{1, {seg(buf(w.g_emb0), c.embed_dim, c.embed_dim)}};
-    ca.L[0] = chain_layer(E, in, 0, wt(p->o_g0tq), p->ng0, S, cn, nullptr, nullptr, &ad, 0, 0, 0);
-    ca.L[1] = chain_layer(E, none, 0, wt(p->embed.wtq[1]), S, 64, cn, nullptr, &zz, nullptr, 1, 0, 0);
-    ca.L[2] = chain_layer(E, none, 0, wt(p->embed.wtq[0]), 64, c.embed_dim, ce, nullptr, nullptr, nullptr, 1, -1, 0);
+    ca.L[0] = chain_layer(E, in, 0, wt(p->blob.o_g0tq), p->blob.ng0, S, cn, nullptr, nullptr, &ad, 0, 0, 0);
+    ca.L[1] = chain_layer(E, none, 0, wt(p->blob.embed.wtq[1]), S, 64, cn, nullptr, &zz, nullptr, 1, 0, 0);
+    ca.L[2] = chain_layer(E, none, 0, wt(p->blob.embed.wtq[0]), 64, c.embed_dim, ce, nullptr, nullptr, nullptr, 1, -1, 0);
     // the epilogue that contracts d (two-body embedding) straight back to the 8 basis functions (ModelPipeline::embed_fused)
     auto contract_embedding = [&](ChainLayer& layer, const T* table) {
       layer.embrev_out = buf(w.trev);
@@ -2803,24 +2797,24 @@ struct Runner {
       // everything in front of the hidden layer of scalar_embed_mlp folded (fold_embed_output; the forward stored a_e, not the embedding):
       // d h = ((d[two-body | w0] @ (W1 G0)^T) + d a_e of the moments) x silu'(h) -- ONE 256 -> 64 layer, 8 steps -- ...
       ca.nlayers = 1;
-      ca.L[0] = chain_layer(E, in, 0, wt(p->o_g0tfq), p->ng0, 64, cn, nullptr, &zz, &ad, 0, 0, 0);
+      ca.L[0] = chain_layer(E, in, 0, wt(p->blob.o_g0tfq), p->blob.ng0, 64, cn, nullptr, &zz, &ad, 0, 0, 0);
       if (p->pipe.embed_fused && p->pipe.fold_embed_table) {
         // ... contracted against the folded two-body table in its epilogue
-        contract_embedding(ca.L[0], wt(p->o_embtab_h));
+        contract_embedding(ca.L[0], wt(p->blob.o_embtab_h));
       } else {
         // ... (three species: no table in the chain's LDS) followed by W0^T -> d emb0 for the edge reverse
         ca.nlayers = 2;
-        ca.L[1] = chain_layer(E, none, 0, wt(p->embed.wtq[0]), 64, c.embed_dim, ce, nullptr, nullptr, nullptr, 1, -1, 0);
+        ca.L[1] = chain_layer(E, none, 0, wt(p->blob.embed.wtq[0]), 64, c.embed_dim, ce, nullptr, nullptr, nullptr, 1, -1, 0);
       }
     } else if (p->pipe.embed_fused && p->pipe.fold_embed_table) {
       // folded table (fold_embed_table): d_h, the output of the second layer, is contracted straight back to the 8 basis functions
       // with T = tab @ W0 -- the layer W0^T and d emb0 do not exist
       ca.nlayers = 2;
-      contract_embedding(ca.L[1], wt(p->o_embtab_h));
+      contract_embedding(ca.L[1], wt(p->blob.o_embtab_h));
     } else if (p->pipe.embed_fused) {
       // d emb0 is contracted straight back to the 8 basis functions in the epilogue and never stored
       ca.L[2].g.c = SegList{1, {seg(nullptr, c.embed_dim, c.embed_dim)}};
-      contract_embedding(ca.L[2], wt(p->o_embtab));
+      contract_embedding(ca.L[2], wt(p->blob.o_embtab));
     }
     return run_chain(ca, "B1");
   }
