@@ -700,12 +700,14 @@ struct FusedFwdArgs {
   float* fcat;     // [E,192] EDGE_FEATURES or nullptr
   float *x2s0, *x2s1;  // [N][D][64]
   float* atom_energy;  // [N]
-  int long_only;       // (host-only, set by launch_fused_fwd like skip_long / fill_done below; placed here so that the fields the
+  int long_only;       // (host-only, set by launch_fused_fwd like skip_long below; placed here so that the fields the
                        //  kernels read keep their offsets -- the compiler's grouping of argument loads, and with it register
                        //  allocation, follows them)
   int32_t* status;     // nullable, host-visible: set to the offending degree when a segment exceeds what the max_degree hint promised
   int mixed;           // with the class lists set: one-tile pass over all atoms (long ones skipped) + team pass over the long ones only
-  int skip_long, fill_done;  // (set by launch_fused_fwd for the two passes of the mixed form)
+  int skip_long, fill_done;  // host-only.  skip_long: set by launch_fused_fwd for the two passes of the mixed form.  fill_done: the energies of the
+                             // atoms outside [atom0, atom_end) are NOT to be filled with their shifts -- set by launch_fused_fwd for the team pass of the
+                             // mixed form (the one-tile pass did it) and by Runner::fused_args for a block of a blocked step (other blocks own them)
   // two-waves-per-SIMD form with the readout-reverse chain in its tail (FusedForm::EightWaveTail; aa_fused8.hip): d EDGE_FEATURES[:, :128] and the
   // gradient of the layer-1 tensor-track scalars leave the forward kernel, the pre-activations of latent 1 / the readout do not
   float* g_fcat;
@@ -801,6 +803,14 @@ int launch_atom_virial(const AtomVirialArgs& a, hipStream_t stream);
 // verifies the aa_graph.atom_begin / atom_end promise (no edge segment outside the block): *status = -2 otherwise
 int launch_graph_hint_check(const int32_t* rowptr, int64_t N, int64_t a0, int64_t a1, int32_t* status, void* atom_energy, void* forces,
                             int esize, hipStream_t stream);
+// Blocked step (aa_model_energy_forces_blocked): row pointers of the sub-graph of the center atoms [a0, a1), whose edges are the
+// slice [lo, hi) of the frame's list: out[i] = clamp(rowptr[i], lo, hi) - lo for i in [0, N].  The clamp would hide a wrong cut from
+// graph_hint_check_kernel, so the cut is verified here: unless rowptr[a0] == lo and rowptr[a1] == hi, *status = -16 - block (host-visible)
+// and *bad = 1 (device memory, read by launch_blocked_finish).
+int launch_block_rowptr(const int32_t* rowptr, int64_t N, int64_t a0, int64_t a1, int32_t lo, int32_t hi, int32_t block, int32_t* out,
+                        int32_t* status, int32_t* bad, hipStream_t stream);
+// last launch of a blocked step: a wrong cut (*bad != 0) turns atom_energy [N] and forces [N,3] (nullable) of the whole frame into NaN
+int launch_blocked_finish(const int32_t* bad, int64_t N, void* atom_energy, void* forces, int esize, hipStream_t stream);
 template <typename T>
 int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t stream);
 
@@ -837,6 +847,7 @@ struct ReadoutArgs {
   void* g_h;           // bwd: [E,H] written
   const void* edge_sum;  // [E] or nullptr: per-edge values already contracted with w (then h/w/act are unused)
   int act_kind;          // AA_ACT_* of the readout MLP (used when act != 0)
+  int64_t atom0;         // readout_reduce: atoms [atom0, N) get their energy written (0 but for the blocks of a blocked step)
 };
 template <typename T>
 int launch_readout_reduce(const ReadoutArgs& a, hipStream_t stream);

@@ -636,7 +636,7 @@ int launch_pair_zbl(const PairZblArgs& a, hipStream_t stream) {
 template <typename T>
 __global__ __launch_bounds__(256) void readout_reduce_kernel(ReadoutArgs a) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t n = int64_t(blockIdx.x) * 4 + wv;
+  const int64_t n = a.atom0 + int64_t(blockIdx.x) * 4 + wv;
   T acc = T(0);
   if (n < a.N) {
     int beg = a.rowptr[n], end = a.rowptr[n + 1];
@@ -808,10 +808,51 @@ int launch_graph_hint_check(const int32_t* rowptr, int64_t N, int64_t a0, int64_
   return AA_OK;
 }
 
+// Blocked step: the rebased row pointers of one block and the check of its cut (aa_common.h, launch_block_rowptr).  Every value
+// written lies in [0, hi - lo] and the array is non-decreasing whatever the cut, so a wrong cut gives wrong numbers (replaced by NaN
+// at the end of the call), never an index outside the block's edge slice.
+__global__ __launch_bounds__(256) void block_rowptr_kernel(const int32_t* rowptr, int64_t N, int64_t a0, int64_t a1, int32_t lo, int32_t hi,
+                                                           int32_t block, int32_t* out, int32_t* status, int32_t* bad) {
+  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (i <= N) {
+    const int32_t r = rowptr[i];
+    out[i] = (r < lo ? lo : (r > hi ? hi : r)) - lo;
+  }
+  if (i == 0 && !(rowptr[a0] == lo && rowptr[a1] == hi)) {
+    // (the first wrong block of the call is the one reported: a cut is shared by two blocks, and both see it)
+    if (*bad == 0) *reinterpret_cast<volatile int32_t*>(status) = -16 - block;
+    *bad = 1;
+  }
+}
+int launch_block_rowptr(const int32_t* rowptr, int64_t N, int64_t a0, int64_t a1, int32_t lo, int32_t hi, int32_t block, int32_t* out,
+                        int32_t* status, int32_t* bad, hipStream_t stream) {
+  hipLaunchKernelGGL(block_rowptr_kernel, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, stream, rowptr, N, a0, a1, lo, hi, block, out,
+                     status, bad);
+  AA_CHECK_HIP(hipGetLastError());
+  return AA_OK;
+}
+
+// Runs LAST in a blocked step: one small block; the fill is the failure path only (as graph_hint_check_kernel)
+__global__ void blocked_finish_kernel(const int32_t* bad, int64_t N, void* atom_energy, void* forces, int esize) {
+  if (*bad == 0) return;
+  for (int64_t i = threadIdx.x; i < 4 * N; i += blockDim.x) {
+    void* dst = i < N ? atom_energy : forces;
+    const int64_t k = i < N ? i : i - N;
+    if (!dst) continue;
+    if (esize == 4) static_cast<float*>(dst)[k] = __builtin_nanf("");
+    else static_cast<double*>(dst)[k] = __builtin_nan("");
+  }
+}
+int launch_blocked_finish(const int32_t* bad, int64_t N, void* atom_energy, void* forces, int esize, hipStream_t stream) {
+  hipLaunchKernelGGL(blocked_finish_kernel, dim3(1), dim3(256), 0, stream, bad, N, atom_energy, forces, esize);
+  AA_CHECK_HIP(hipGetLastError());
+  return AA_OK;
+}
+
 template <typename T>
 int launch_readout_reduce(const ReadoutArgs& a, hipStream_t stream) {
-  if (a.N == 0) return AA_OK;
-  hipLaunchKernelGGL(readout_reduce_kernel<T>, dim3((unsigned)((a.N + 3) / 4)), dim3(256), 0, stream, a);
+  if (a.N <= a.atom0) return AA_OK;
+  hipLaunchKernelGGL(readout_reduce_kernel<T>, dim3((unsigned)((a.N - a.atom0 + 3) / 4)), dim3(256), 0, stream, a);
   AA_CHECK_HIP(hipGetLastError());
   return AA_OK;
 }

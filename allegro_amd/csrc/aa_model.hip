@@ -361,6 +361,8 @@ struct StepInputs {
   int64_t atom0, atom_end;  // the active block: the atom-block hint, or every atom
   int64_t max_degree;       // aa_graph::max_degree, 0 = unknown
   bool pair_zbl;            // aa_model_plan_set_pair_zbl: the plan carries a ZBL pair potential
+  bool block;               // internal, off for every public single-step entry point: the step is one block of a blocked step
+                            // (aa_model_energy_forces_blocked)
 };
 
 enum class ForwardKind {
@@ -398,6 +400,9 @@ struct StepPlan {
   bool gather;                          // deterministic force assembly over the transposed CSR (off: atomics)
   bool zero_gsh, zero_forces;           // the reverse pass accumulates into d Y / the forces: zeroed first
   bool pair_zbl;                        // ZBL pair potential: one launch behind the forward (energy only) or in edge_tail (force step)
+  bool block;                           // one block of a blocked step (the ONE place that says so; Runner reads it): only the block's atoms get their
+                                        // energy written; with forces dvec / vec rows go to the frame-wide arrays in the gather form (no atomics) and the
+                                        // caller assembles the forces
 
   bool fused() const { return forward == ForwardKind::FusedOneTile || forward == ForwardKind::FusedTeam || forward == ForwardKind::FusedMixed; }
   // did the forward of this step leave a_e in the embedding's slot (folded first stage / env weights in the reverse)?
@@ -506,7 +511,8 @@ static StepPlan choose_step(const ModelPipeline& pipe, const aa_plan_options& op
   s.proj_reverse = s.proj_forward && in.with_forces;
 
   // ---- what the reverse pass sums into ----
-  s.gather = in.transposed_csr;
+  s.block = in.block;
+  s.gather = in.transposed_csr || (s.block && in.with_forces);
   // spec path with u <= 64 writes every g_sh slot with plain stores; otherwise slots are accumulated into
   s.zero_gsh = in.with_forces && !((pipe.channel_minor() && c.num_tensor <= 64) || pipe.tp_op >= 0);
   s.zero_forces = in.with_forces && !s.gather;
@@ -786,7 +792,8 @@ struct aa_model_plan {
   // Host-visible status word (pinned host memory, written by kernels, read by the host without a synchronisation): a step
   // whose graph contradicts the caller's hints (aa_graph.max_degree, atom_begin / atom_end) sets it, the offending atoms'
   // energies become NaN, and the NEXT aa_model_energy_forces on the plan -- or aa_model_check, which synchronises first --
-  // returns AA_ERR_INVALID.  > 0: degree of a center atom beyond max_degree; -2: edges outside [atom_begin, atom_end).
+  // returns AA_ERR_INVALID.  > 0: degree of a center atom beyond max_degree; -2: edges outside [atom_begin, atom_end);
+  // <= -16: block -16 - v of a blocked step was cut at the wrong edge.
   int32_t* status = nullptr;
 };
 
@@ -803,6 +810,9 @@ static int consume_status(const aa_model_plan* plan, const char* who) {
   if (v > 0)
     snprintf(msg, sizeof msg, "%s: a step on this plan met a center atom with %d edges, more than aa_graph.max_degree promised "
              "(its energy was set to NaN; pass the true maximum, or 0 for \"unknown\")", who, int(v));
+  else if (v <= -16)
+    snprintf(msg, sizeof msg, "%s: a blocked step on this plan was given a wrong cut for block %d: block_edges[b] / block_edges[b + 1] are not "
+             "rowptr[block_atoms[b]] / rowptr[block_atoms[b + 1]] (energies and forces of the frame were set to NaN)", who, int(-16 - v));
   else
     snprintf(msg, sizeof msg, "%s: a step on this plan met edges whose center lies outside [aa_graph.atom_begin, atom_end)", who);
   return fail(AA_ERR_INVALID, msg);
@@ -1571,6 +1581,37 @@ extern "C" size_t aa_model_workspace_bytes(const aa_model_plan* plan, int64_t N,
   return layout_workspace(plan, N, E, with_forces).total;
 }
 
+// Blocked step (aa_model_energy_forces_blocked): ONE arena -- the layout above at the edge count of the largest block, used by one
+// block after the other -- followed by the frame part: the rebased row pointers of the block in flight [N+1], the flag of the cut
+// check, and on a force step the two frame-wide [E,4] arrays every block writes its rows of.
+struct BlockedWorkspace {
+  Workspace arena;
+  size_t rowptr, bad, vec, dvec, total;
+};
+static BlockedWorkspace layout_blocked(const aa_model_plan* p, int64_t N, int64_t E, int64_t max_block_edges, int with_forces) {
+  BlockedWorkspace b{};
+  b.arena = layout_workspace(p, N, max_block_edges, with_forces);
+  size_t o = b.arena.total;
+  auto take = [&](size_t bytes) {
+    size_t r = o;
+    o += (bytes + 255) / 256 * 256;
+    return r;
+  };
+  b.rowptr = take(sizeof(int32_t) * (size_t(N) + 1));
+  b.bad = take(sizeof(int32_t));
+  if (with_forces) {
+    b.vec = take(size_t(E) * 4 * p->esize());
+    b.dvec = take(size_t(E) * 4 * p->esize());
+  }
+  b.total = o;
+  return b;
+}
+
+extern "C" size_t aa_model_blocked_workspace_bytes(const aa_model_plan* plan, int64_t N, int64_t E, int64_t max_block_edges, int with_forces) {
+  if (!plan || N < 0 || E < 0 || max_block_edges < 0) return 0;
+  return layout_blocked(plan, N, E, std::min(max_block_edges, E), with_forces).total;
+}
+
 // ------------------------------------------------------------------------------------------------
 // pipeline
 // ------------------------------------------------------------------------------------------------
@@ -1613,6 +1654,12 @@ struct Runner {
   StageProfile* prof = nullptr;
   StepPlan sp{};  // the launches of this step (choose_step): set by run_model, read everywhere below
   void* e_out = nullptr;  // atom_energy of this step (what the pair potential adds to)
+  // one block of a blocked force step (StepPlan::block): the [E,4] rows of vec / dvec are those of the frame-wide arrays (the workspace
+  // slots of the same name stay unused)
+  void* frame_vec = nullptr;
+  void* frame_dvec = nullptr;
+  T* vec_rows() const { return frame_vec ? static_cast<T*>(frame_vec) : buf(w.vec); }
+  T* dvec_rows() const { return frame_dvec ? static_cast<T*>(frame_dvec) : buf(w.dvec); }
 
   // per_edge / per_atom: operand elements the launch must move (each distinct operand row once); see DESIGN.md §5
   int mark(const char* name, double per_edge = 0, double per_atom = 0, double flops = 0) {
@@ -1747,7 +1794,7 @@ struct Runner {
     a.embed_kind = c.embed_kind;
     a.spline_span = c.spline_span;
     a.emb_tab = p->pipe.two_body_table ? wt(p->blob.o_embtab) : nullptr;
-    a.vec = buf(w.vec);
+    a.vec = vec_rows();
     a.sh = buf(w.sh);
     a.emb0 = buf(w.emb0);
     return a;
@@ -2054,7 +2101,7 @@ struct Runner {
     a.ro_factor = float(1.0 / std::sqrt(2.0 * c.avg_num_neighbors));
     a.scales = c.has_scales ? wf(p->blob.o_scales) : nullptr;
     a.shifts = c.has_shifts ? wf(p->blob.o_shifts) : nullptr;
-    a.vec = bf(w.vec);
+    a.vec = reinterpret_cast<float*>(vec_rows());
     a.sh = bf(w.sh);
     a.se_h = bf(w.se_h[0]);
     a.emb = bf(w.emb);
@@ -2067,6 +2114,7 @@ struct Runner {
     a.x2s1 = bf(w.x2s[1]);
     a.atom_energy = static_cast<float*>(atom_energy);
     a.status = p->status;
+    a.fill_done = sp.block ? 1 : 0;  // (a block leaves the energies of the other blocks' atoms alone)
     return a;
   }
   const float* wf(size_t off) const { return reinterpret_cast<const float*>(wt(off)); }
@@ -2387,6 +2435,10 @@ struct Runner {
       }
     }
     ReadoutArgs ra = readout_args(g, atom_energy);
+    if (sp.block) {
+      ra.atom0 = atom_begin(g);
+      ra.N = atom_end(g);
+    }
     if (sp.readout_grad_in_reduce) ra.g_h = buf(w.g_ro_h[c.readout_mlp_depth - 1]);
     if (int rc = launch_readout_reduce<T>(ra, stream)) return rc;
     return mark("readout_reduce", (p->pipe.chains() ? 1 : (c.readout_mlp_depth > 0 ? c.readout_mlp_width : SL1)) * (sp.readout_grad_in_reduce ? 2.0 : 1.0), 1);
@@ -2418,7 +2470,7 @@ struct Runner {
     a.tab = p->zbl_tab;
     a.poly_p = p->zbl_poly_p;
     a.atom_energy = e_out;
-    a.dvec = forces ? buf(w.dvec) : nullptr;
+    a.dvec = forces ? dvec_rows() : nullptr;
     a.forces = (forces && !sp.gather) ? forces : nullptr;
     if (int rc = launch_pair_zbl<T>(a, stream)) return rc;
     // per edge: neighbor index + its position and type (+ the shift vector), on a force step the dvec row read and written
@@ -2437,13 +2489,13 @@ struct Runner {
     eb.forces = forces;
     if (p->pipe.embed_fused) eb.t_in = buf(w.trev);
     const bool gather = sp.gather;
-    eb.dvec = buf(w.dvec);
+    eb.dvec = dvec_rows();
     eb.gather = gather ? 1 : 0;
     if (int rc = launch_edge_backward<T>(eb, stream)) return rc;
     if (int rc = mark("edge_backward", 8.0 / sizeof(T) + 4 + (p->pipe.embed_fused ? c.num_bessels : c.embed_dim) + double(num_gsh) * p->D + (gather ? 4 : 6))) return rc;
     if (sp.pair_zbl)
       if (int rc = pair_zbl(g, pos, forces)) return rc;
-    if (gather) {
+    if (gather && !sp.block) {
       // deterministic force assembly: per atom, own segment minus transposed segment, fixed order (no atomics)
       ForceGatherArgs fg{N, g->rowptr, g->t_rowptr, g->t_perm, buf(w.dvec), forces};
       if (int rc = launch_force_gather<T>(fg, stream)) return rc;
@@ -2834,11 +2886,23 @@ struct Runner {
   }
 };
 
+// what makes a step one block of a blocked step: rows of the frame-wide vec / dvec arrays at the block's first edge (force steps; both
+// null on an energy-only one)
+struct BlockStep {
+  void* vec = nullptr;
+  void* dvec = nullptr;
+};
+
 template <typename T>
 int run_model(const aa_model_plan* p, const void* dev_weights, const aa_graph* g, const void* pos, void* workspace,
-              size_t ws_bytes, void* atom_energy, void* forces, hipStream_t stream, StageProfile* prof = nullptr) {
+              size_t ws_bytes, void* atom_energy, void* forces, hipStream_t stream, StageProfile* prof = nullptr,
+              const BlockStep* blk = nullptr) {
   Runner<T> r;
   r.prof = prof;
+  if (blk) {
+    r.frame_vec = blk->vec;
+    r.frame_dvec = blk->dvec;
+  }
   r.p = p;
   r.wts = static_cast<const T*>(dev_weights);
   r.ws = static_cast<char*>(workspace);
@@ -2860,12 +2924,13 @@ int run_model(const aa_model_plan* p, const void* dev_weights, const aa_graph* g
   in.atom_end = r.atom_end(g);
   in.max_degree = g->max_degree;
   in.pair_zbl = p->zbl_tab != nullptr;
+  in.block = blk != nullptr;
   int cus = 0;  // (asked only where a decision reads it)
   if (wide_one_tile_pass(p->pipe, choose_forward(p->pipe, p->opt, p->cfg, in)) && (cus = device_cu_count()) < 0) return cus;
   r.sp = choose_step(p->pipe, p->opt, p->cfg, in, cus);
-  if (p->ev_wait) AA_CHECK_HIP(hipStreamWaitEvent(stream, (hipEvent_t)(uintptr_t)(p->ev_wait), 0));
+  if (p->ev_wait && !blk) AA_CHECK_HIP(hipStreamWaitEvent(stream, (hipEvent_t)(uintptr_t)(p->ev_wait), 0));
   if (int rc = r.forward(g, pos, atom_energy)) return rc;
-  if (p->ev_record) AA_CHECK_HIP(hipEventRecord((hipEvent_t)(uintptr_t)(p->ev_record), stream));
+  if (p->ev_record && !blk) AA_CHECK_HIP(hipEventRecord((hipEvent_t)(uintptr_t)(p->ev_record), stream));
   if (forces) {
     if (int rc = r.backward(g, pos, forces)) return rc;  // (ends in edge_tail, which launches the pair potential of a force step)
   } else if (r.sp.pair_zbl) {
@@ -2873,7 +2938,8 @@ int run_model(const aa_model_plan* p, const void* dev_weights, const aa_graph* g
   }
   // the atom-block hint is the caller's promise (per-atom kernels skip the rest): two row pointers verify it on the device, as the
   // LAST launch of the step, so that a broken promise also turns this step's energies and forces into NaN
-  if (g->atom_end > g->atom_begin && (g->atom_begin > 0 || g->atom_end < g->num_atoms) && p->status)
+  // (a block of a blocked step: its row pointers are clamped to the block, launch_block_rowptr has checked the cut)
+  if (!blk && g->atom_end > g->atom_begin && (g->atom_begin > 0 || g->atom_end < g->num_atoms) && p->status)
     if (int rc = launch_graph_hint_check(g->rowptr, g->num_atoms, g->atom_begin, g->atom_end, p->status, atom_energy, forces, int(sizeof(T)), stream))
       return rc;
   return AA_OK;
@@ -2985,6 +3051,134 @@ extern "C" int aa_model_atom_virial(const aa_model_plan* plan, const aa_graph* g
   if (w.total > workspace_bytes) return fail(AA_ERR_WORKSPACE, "aa_model_atom_virial: workspace too small (was it sized with forces?)");
   char* base = static_cast<char*>(workspace);
   AtomVirialArgs a{graph->num_atoms, graph->rowptr, graph->t_rowptr, graph->t_perm, base + w.dvec, base + w.vec, cc, cn, out_n9};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return plan->cfg.dtype == AA_F32 ? launch_atom_virial<float>(a, s) : launch_atom_virial<double>(a, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// blocked step: the frame one block of center atoms after the other, in one arena
+// ------------------------------------------------------------------------------------------------
+namespace {
+template <typename T>
+int run_blocked(const aa_model_plan* p, const void* dev_weights, const aa_graph* g, const void* pos, int32_t num_blocks, const int64_t* block_atoms,
+                const int64_t* block_edges, const BlockedWorkspace& bw, char* base, void* atom_energy, void* forces, hipStream_t stream) {
+  const int64_t N = g->num_atoms;
+  int32_t* rowptr_b = reinterpret_cast<int32_t*>(base + bw.rowptr);
+  int32_t* bad = reinterpret_cast<int32_t*>(base + bw.bad);
+  if (p->opt.poison_workspace) AA_CHECK_HIP(hipMemsetAsync(base, 0xFF, bw.total, stream));  // (the frame part too; every block poisons the arena again)
+  AA_CHECK_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), stream));
+  for (int32_t b = 0; b < num_blocks; ++b) {
+    const int64_t a0 = block_atoms[b], a1 = block_atoms[b + 1], lo = block_edges[b], hi = block_edges[b + 1];
+    if (a1 == a0 && hi == lo) continue;  // nothing to evaluate (its two cuts are those of its neighbours, which check them)
+    if (int rc = launch_block_rowptr(g->rowptr, N, a0, a1, int32_t(lo), int32_t(hi), b, rowptr_b, p->status, bad, stream)) return rc;
+    if (a1 == a0) continue;  // (edges without an atom: a wrong cut, just reported)
+    aa_graph sub = *g;
+    sub.num_edges = hi - lo;
+    sub.center = g->center ? g->center + lo : nullptr;
+    sub.nbr = g->nbr ? g->nbr + lo : nullptr;
+    sub.rowptr = rowptr_b;
+    sub.shift_vec = g->shift_vec ? static_cast<const char*>(g->shift_vec) + size_t(lo) * 3 * sizeof(T) : nullptr;
+    sub.t_rowptr = nullptr;  // (no block assembles forces)
+    sub.t_perm = nullptr;
+    sub.atom_begin = a0;
+    sub.atom_end = a1;
+    BlockStep blk{};
+    if (forces) {
+      blk.vec = base + bw.vec + size_t(lo) * 4 * sizeof(T);
+      blk.dvec = base + bw.dvec + size_t(lo) * 4 * sizeof(T);
+    }
+    if (int rc = run_model<T>(p, dev_weights, &sub, pos, base, bw.arena.total, atom_energy, forces, stream, nullptr, &blk)) return rc;
+  }
+  if (forces) {
+    // ONE deterministic force assembly over the frame arrays: the summation order of the unblocked step with a transposed CSR
+    ForceGatherArgs fg{N, g->rowptr, g->t_rowptr, g->t_perm, base + bw.dvec, forces};
+    if (int rc = launch_force_gather<T>(fg, stream)) return rc;
+  }
+  return launch_blocked_finish(bad, N, atom_energy, forces, int(sizeof(T)), stream);
+}
+}  // namespace
+
+extern "C" int aa_model_energy_forces_blocked(const aa_model_plan* plan, const void* dev_weights, const aa_graph* graph, const void* pos,
+                                              int32_t num_blocks, const int64_t* block_atoms, const int64_t* block_edges, void* workspace,
+                                              size_t workspace_bytes, void* atom_energy, void* forces, aa_stream stream) {
+  const char* who = "aa_model_energy_forces_blocked";
+  AA_REQUIRE(plan && dev_weights && graph && pos && atom_energy && block_atoms && block_edges, "aa_model_energy_forces_blocked: null argument");
+  AA_REQUIRE(graph->num_atoms >= 0 && graph->num_edges >= 0 && graph->num_edges < (int64_t(1) << 31),
+             "aa_model_energy_forces_blocked: graph too large for int32 edge ids");
+  AA_REQUIRE(graph->num_edges == 0 || (graph->center && graph->nbr), "aa_model_energy_forces_blocked: null edge arrays");
+  AA_REQUIRE(graph->rowptr && graph->types, "aa_model_energy_forces_blocked: null rowptr/types");
+  AA_REQUIRE(workspace, "aa_model_energy_forces_blocked: null workspace");
+  AA_REQUIRE(num_blocks >= 1, "aa_model_energy_forces_blocked: num_blocks must be at least 1");
+  if (plan->sg.enabled)
+    return fail(AA_ERR_INVALID, std::string(who) + ": the blocked step is not captured into a hipGraph (aa_model_plan_enable_graph is on for this plan; "
+                                                   "its launch list depends on the block cuts)");
+  if (plan->taps)
+    return fail(AA_ERR_INVALID, std::string(who) + ": the blocked step does not serve the debug taps (aa_model_plan_enable_taps is on for this plan; "
+                                                   "the arena holds one block at a time)");
+  if (forces && !(graph->t_rowptr && (graph->t_perm || graph->num_edges == 0)))
+    return fail(AA_ERR_INVALID, std::string(who) + ": forces are assembled once over the whole frame through the transposed CSR "
+                                                   "(aa_graph.t_rowptr / t_perm, aa_graph_transpose); there is no atomics fallback");
+  const int64_t N = graph->num_atoms, E = graph->num_edges;
+  if (block_atoms[0] != 0 || block_atoms[num_blocks] != N)
+    return fail(AA_ERR_INVALID, std::string(who) + ": block_atoms must run from 0 to num_atoms (block_atoms[0] = " + std::to_string(block_atoms[0]) +
+                                    ", block_atoms[" + std::to_string(num_blocks) + "] = " + std::to_string(block_atoms[num_blocks]) + ", num_atoms = " +
+                                    std::to_string(N) + ")");
+  if (block_edges[0] != 0 || block_edges[num_blocks] != E)
+    return fail(AA_ERR_INVALID, std::string(who) + ": block_edges must run from 0 to num_edges (block_edges[0] = " + std::to_string(block_edges[0]) +
+                                    ", block_edges[" + std::to_string(num_blocks) + "] = " + std::to_string(block_edges[num_blocks]) + ", num_edges = " +
+                                    std::to_string(E) + ")");
+  int64_t cap = 0;
+  for (int32_t b = 0; b < num_blocks; ++b) {
+    if (block_atoms[b + 1] < block_atoms[b])
+      return fail(AA_ERR_INVALID, std::string(who) + ": block_atoms must be non-decreasing (block " + std::to_string(b) + ")");
+    if (block_edges[b + 1] < block_edges[b])
+      return fail(AA_ERR_INVALID, std::string(who) + ": block_edges must be non-decreasing (block " + std::to_string(b) + ")");
+    cap = std::max(cap, block_edges[b + 1] - block_edges[b]);
+  }
+  if (int rc = consume_status(plan, who)) return rc;  // (an EARLIER step contradicted its graph hints or its cuts)
+  const BlockedWorkspace bw = layout_blocked(plan, N, E, cap, forces != nullptr);
+  if (bw.total > workspace_bytes)
+    return fail(AA_ERR_WORKSPACE, std::string(who) + ": workspace too small (aa_model_blocked_workspace_bytes at the largest block, " + std::to_string(cap) +
+                                      " edges, asks for " + std::to_string(bw.total) + " bytes)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(workspace);
+  return plan->cfg.dtype == AA_F32
+             ? run_blocked<float>(plan, dev_weights, graph, pos, num_blocks, block_atoms, block_edges, bw, base, atom_energy, forces, s)
+             : run_blocked<double>(plan, dev_weights, graph, pos, num_blocks, block_atoms, block_edges, bw, base, atom_energy, forces, s);
+}
+
+extern "C" int aa_model_blocked_virial(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges, void* workspace,
+                                       size_t workspace_bytes, void* virial9, aa_stream stream) {
+  AA_REQUIRE(plan && graph && workspace && virial9, "aa_model_blocked_virial: null argument");
+  AA_REQUIRE(max_block_edges >= 0, "aa_model_blocked_virial: negative max_block_edges");
+  const BlockedWorkspace bw = layout_blocked(plan, graph->num_atoms, graph->num_edges, std::min(max_block_edges, graph->num_edges), 1);
+  if (bw.total > workspace_bytes) return fail(AA_ERR_WORKSPACE, "aa_model_blocked_virial: workspace too small (was it sized with forces, at this max_block_edges?)");
+  char* base = static_cast<char*>(workspace);
+  VirialArgs a{graph->num_edges, base + bw.dvec, base + bw.vec, reinterpret_cast<double*>(base + bw.arena.vir_part), virial9};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return plan->cfg.dtype == AA_F32 ? launch_virial<float>(a, s) : launch_virial<double>(a, s);
+}
+
+extern "C" int aa_model_blocked_atom_virial(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges, void* workspace,
+                                            size_t workspace_bytes, int attribution, void* out_n9, aa_stream stream) {
+  AA_REQUIRE(plan && graph && workspace && out_n9, "aa_model_blocked_atom_virial: null argument");
+  AA_REQUIRE(max_block_edges >= 0, "aa_model_blocked_atom_virial: negative max_block_edges");
+  double cc, cn;
+  switch (attribution) {
+    case AA_ATOM_VIRIAL_CENTER: cc = 1.0, cn = 0.0; break;
+    case AA_ATOM_VIRIAL_NEIGHBOR: cc = 0.0, cn = 1.0; break;
+    case AA_ATOM_VIRIAL_SPLIT: cc = cn = 0.5; break;
+    default: return fail(AA_ERR_INVALID, "aa_model_blocked_atom_virial: unknown attribution " + std::to_string(attribution) +
+                                             " (AA_ATOM_VIRIAL_CENTER, _NEIGHBOR or _SPLIT)");
+  }
+  if (cn != 0.0 && !(graph->t_rowptr && (graph->t_perm || graph->num_edges == 0)))
+    return fail(AA_ERR_INVALID, "aa_model_blocked_atom_virial: the neighbor and split attributions need the transposed CSR "
+                                "(aa_graph.t_rowptr / t_perm, aa_graph_transpose)");
+  const BlockedWorkspace bw = layout_blocked(plan, graph->num_atoms, graph->num_edges, std::min(max_block_edges, graph->num_edges), 1);
+  if (bw.total > workspace_bytes)
+    return fail(AA_ERR_WORKSPACE, "aa_model_blocked_atom_virial: workspace too small (was it sized with forces, at this max_block_edges?)");
+  char* base = static_cast<char*>(workspace);
+  AtomVirialArgs a{graph->num_atoms, graph->rowptr, graph->t_rowptr, graph->t_perm, base + bw.dvec, base + bw.vec, cc, cn, out_n9};
   hipStream_t s = static_cast<hipStream_t>(stream);
   return plan->cfg.dtype == AA_F32 ? launch_atom_virial<float>(a, s) : launch_atom_virial<double>(a, s);
 }

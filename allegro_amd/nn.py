@@ -477,6 +477,39 @@ class PreparedGraph:
             self.t_rowptr = torch.zeros(num_atoms + 1, dtype=torch.int32, device=edge_index.device)
             self.t_rowptr[1:] = torch.cumsum(torch.bincount(edge_index[1], minlength=num_atoms), 0).to(torch.int32)
 
+    def rowptr_host(self):
+        """The row pointers as a host int64 array: ONE device read per graph, kept."""
+        rp = getattr(self, "_rowptr_host", None)
+        if rp is None:
+            import numpy as np
+
+            rp = self._rowptr_host = self.rowptr.cpu().numpy().astype(np.int64)
+        return rp
+
+    def blocks(self, max_edges: int):
+        """Cuts the frame into contiguous blocks of center atoms for the block-wise step (`aa_model_energy_forces_blocked`,
+        `HipAllegroModel.energy_forces(..., max_block_edges=)`): greedy, every block takes as many atoms as fit `max_edges` edges
+        (atoms without edges ride along with the block in front of them).  Returns (block_atoms, block_edges), host int64 arrays
+        [B+1] with block_edges[b] = rowptr[block_atoms[b]].  One atom with more than `max_edges` edges cannot be cut: ValueError."""
+        import numpy as np
+
+        rp, n = self.rowptr_host(), self.num_atoms
+        max_edges = int(max_edges)
+        deg = np.diff(rp)
+        if n and int(deg.max()) > max_edges:
+            a = int(deg.argmax())
+            raise ValueError(f"atom {a} has {int(deg[a])} edges, more than max_edges = {max_edges}: a block holds whole atoms")
+        if max_edges < 0:
+            raise ValueError(f"max_edges must not be negative, got {max_edges}")
+        cuts = [0]
+        while cuts[-1] < n:
+            # the last atom boundary whose row pointer is within max_edges of the block's first edge (>= one atom: its degree fits)
+            cuts.append(min(n, int(np.searchsorted(rp, rp[cuts[-1]] + max_edges, side="right")) - 1))
+        if len(cuts) == 1:
+            cuts.append(n)  # (no atoms: one empty block)
+        block_atoms = np.asarray(cuts, dtype=np.int64)
+        return block_atoms, rp[block_atoms].copy()
+
     def c_struct(self) -> _lib.Graph:
         return _lib.Graph(self.num_atoms, self.num_edges, self.center.data_ptr(), self.nbr.data_ptr(),
                           self.rowptr.data_ptr(), self.types.data_ptr(),
@@ -484,6 +517,15 @@ class PreparedGraph:
                           self.t_rowptr.data_ptr() if self.t_rowptr is not None else None,
                           self.t_perm.data_ptr() if self.t_perm is not None else None,
                           self.atom_begin, self.atom_end, self.max_degree)
+
+
+def _max_degree(graph: PreparedGraph) -> int:
+    """Largest edge segment of `graph`: its hint where the graph carries one, else from the host copy of the row pointers."""
+    if graph.max_degree > 0 or graph.num_edges == 0:
+        return int(graph.max_degree)
+    import numpy as np
+
+    return int(np.diff(graph.rowptr_host()).max())
 
 
 def _nl_types(atom_types: torch.Tensor, cutoffs, num_atoms: int, device, what: str):
@@ -830,6 +872,7 @@ class HipAllegroModel(torch.nn.Module):
         # `_plan_handle` / `_blob` / `_workspace` always refer to the device of the current call (`_select_device`)
         self._per_device: Dict[int, dict] = {}
         self._plan_handle = None
+        self._blocked = None  # (max_block_edges, with_forces) when the last step on the current device was a blocked one
         self._plan_keep = None
         self._blob: Optional[torch.Tensor] = None
         self._blob_key = None
@@ -894,13 +937,14 @@ class HipAllegroModel(torch.nn.Module):
                 except Exception:
                     pass
         self._per_device = {}
-        self._plan_handle = self._plan_keep = self._blob = self._blob_key = self._workspace = self._cur_dev = None
+        self._plan_handle = self._plan_keep = self._blob = self._blob_key = self._workspace = self._cur_dev = self._blocked = None
 
     def _stash_device_state(self):
         if self._cur_dev is not None:
             self._per_device[self._cur_dev] = dict(plan=self._plan_handle, keep=self._plan_keep, blob=self._blob,
                                                    blob_key=self._blob_key, ws=self._workspace,
-                                                   hip_graph=getattr(self, "_hip_graph", False), out=getattr(self, "_out", None))
+                                                   hip_graph=getattr(self, "_hip_graph", False), out=getattr(self, "_out", None),
+                                                   blocked=self._blocked)
 
     def _select_device(self, device) -> None:
         """Switch the per-device state (plan, packed weights, workspace) to `device`."""
@@ -914,6 +958,7 @@ class HipAllegroModel(torch.nn.Module):
         self._plan_handle, self._plan_keep = st.get("plan"), st.get("keep")
         self._blob, self._blob_key, self._workspace = st.get("blob"), st.get("blob_key"), st.get("ws")
         self._hip_graph, self._out = st.get("hip_graph", False), st.get("out")
+        self._blocked = st.get("blocked")  # (what the workspace of THIS device holds)
         self._cur_dev = idx
 
     def _sd(self) -> Dict[str, torch.Tensor]:
@@ -1084,16 +1129,80 @@ class HipAllegroModel(torch.nn.Module):
     def prepare_graph(self, edge_index, atom_types, num_atoms, shift_vec=None) -> PreparedGraph:
         return PreparedGraph(edge_index, atom_types, num_atoms, shift_vec, lib=self._bound_lib)
 
-    def energy_forces(self, pos: torch.Tensor, graph: PreparedGraph, with_forces: bool = True):
-        """One pass of the hot path: returns (atom_energy [N], forces [N,3] | None)."""
+    def energy_forces(self, pos: torch.Tensor, graph: PreparedGraph, with_forces: bool = True, max_block_edges: Optional[int] = None):
+        """One pass of the hot path: returns (atom_energy [N], forces [N,3] | None).
+        `max_block_edges`: evaluate the frame block by block (`graph.blocks(max_block_edges)`, `energy_forces_blocks`) in a workspace
+        sized for the largest block instead of the frame -- same results, for frames whose per-edge workspace does not fit the device."""
+        if max_block_edges is not None:
+            block_atoms, block_edges = graph.blocks(max_block_edges)
+            return self.energy_forces_blocks(pos, graph, block_atoms, block_edges, with_forces)
         lib = self._get_lib()
         _require_gpu(lib, pos, "HipAllegroModel")
         assert pos.dtype == self.dtype, f"positions must be {self.dtype}"
         with _device_ctx(pos.device):
             return self._energy_forces_on_device(lib, pos, graph, with_forces)
 
+    def energy_forces_blocks(self, pos: torch.Tensor, graph: PreparedGraph, block_atoms, block_edges, with_forces: bool = True):
+        """The block-wise step on explicit cuts (`aa_model_energy_forces_blocked`): block b owns the center atoms
+        [block_atoms[b], block_atoms[b+1]) and the edges [block_edges[b], block_edges[b+1]) of `graph`, the whole frame.  Forces are
+        assembled once over the frame through the graph's transposed CSR (bit-reproducible).  `virial`, `atom_virial` and
+        `heat_flux_potential` then read what this call left behind.  Not available with `enable_hip_graph` / `enable_debug_taps`."""
+        import numpy as np
+
+        lib = self._get_lib()
+        _require_gpu(lib, pos, "HipAllegroModel")
+        assert pos.dtype == self.dtype, f"positions must be {self.dtype}"
+        block_atoms = np.ascontiguousarray(block_atoms, dtype=np.int64)
+        block_edges = np.ascontiguousarray(block_edges, dtype=np.int64)
+        if block_atoms.ndim != 1 or block_atoms.shape != block_edges.shape or block_atoms.shape[0] < 2:
+            raise ValueError("block_atoms and block_edges must be two [B+1] arrays, B >= 1")
+        cap = int(max(0, min(graph.num_edges, np.diff(block_edges).max())))
+        i64p = C.POINTER(C.c_int64)
+        with _device_ctx(pos.device):
+            self._select_device(pos.device)
+            self._ensure_plan()
+            self._ensure_weights(pos.device)
+            N, E = graph.num_atoms, graph.num_edges
+            need = lib.lib.aa_model_blocked_workspace_bytes(self._plan_handle, N, E, cap, int(with_forces))
+            if self._workspace is None or self._workspace.numel() < need or self._workspace.device != pos.device:
+                self._workspace = None
+                self._workspace = torch.empty(need + need // 16 + (1 << 20), dtype=torch.uint8, device=pos.device)
+            pos = pos.detach().contiguous()
+            e_atom = torch.empty(N, dtype=self.dtype, device=pos.device)
+            forces = torch.empty((N, 3), dtype=self.dtype, device=pos.device) if with_forces else None
+            g = graph.c_struct()
+            self._blocked = None
+            lib.check(lib.lib.aa_model_energy_forces_blocked(self._plan_handle, self._blob.data_ptr(), C.byref(g), pos.data_ptr(),
+                                                             block_atoms.shape[0] - 1, block_atoms.ctypes.data_as(i64p),
+                                                             block_edges.ctypes.data_as(i64p), self._workspace.data_ptr(),
+                                                             self._workspace.numel(), e_atom.data_ptr(),
+                                                             forces.data_ptr() if with_forces else None, _stream_ptr(pos)),
+                      "aa_model_energy_forces_blocked")
+            self._blocked = (cap, bool(with_forces))  # (virial / atom_virial follow the kind of step that ran last)
+        return e_atom, forces
+
+    def max_block_edges_for(self, graph: PreparedGraph, budget_bytes: int, with_forces: bool = True) -> int:
+        """The largest `max_block_edges` whose blocked workspace (`aa_model_blocked_workspace_bytes`) fits `budget_bytes` for `graph`;
+        raises when even blocks of one atom (a cap of the graph's largest degree) do not."""
+        lib = self._get_lib()
+        self._ensure_plan()
+        N, E = graph.num_atoms, graph.num_edges
+        size = lambda cap: lib.lib.aa_model_blocked_workspace_bytes(self._plan_handle, N, E, cap, int(with_forces))  # noqa: E731
+        lo = min(E, int(_max_degree(graph)))
+        if size(lo) > budget_bytes:
+            raise ValueError(f"a blocked workspace for one-atom blocks ({lo} edges) takes {size(lo)} bytes, more than the budget of {int(budget_bytes)}")
+        hi = E
+        while lo < hi:  # (the size function is monotone in the cap: bisection for the last cap that fits)
+            mid = (lo + hi + 1) // 2
+            if size(mid) <= budget_bytes:
+                lo = mid
+            else:
+                hi = mid - 1
+        return lo
+
     def _energy_forces_on_device(self, lib, pos, graph, with_forces):
         self._select_device(pos.device)
+        self._blocked = None  # (virial / atom_virial follow the kind of step that ran last)
         self._ensure_plan()
         self._ensure_weights(pos.device)
         N, E = graph.num_atoms, graph.num_edges
@@ -1148,12 +1257,29 @@ class HipAllegroModel(torch.nn.Module):
         """dE/d(strain) [3,3] of the LAST `energy_forces(..., with_forces=True)` call on `graph` (stress = virial / volume,
         nequip ForceStressOutput; LAMMPS' virial is its negative)."""
         lib = self._get_lib()
+        if getattr(self, "_plan_handle", None) is None or self._workspace is None:
+            raise RuntimeError("virial reads what a step with forces left behind: call energy_forces first")
         out = torch.empty(9, dtype=self.dtype, device=self._workspace.device)
         g = graph.c_struct()
         with _device_ctx(out.device):
             return self._virial_on_device(lib, g, out)
 
+    def _blocked_cap_for(self, what: str) -> Optional[int]:
+        """`max_block_edges` of the blocked step the current device's workspace holds, None after an unblocked step."""
+        if self._blocked is None:
+            return None
+        cap, with_forces = self._blocked
+        if not with_forces:
+            raise RuntimeError(f"{what} reads what a step with forces left behind, and the last step was a blocked energy-only one "
+                               "(it keeps no frame-wide edge arrays): call energy_forces with forces first")
+        return cap
+
     def _virial_on_device(self, lib, g, out):
+        cap = self._blocked_cap_for("virial")
+        if cap is not None:  # the last step on this device was a blocked one
+            lib.check(lib.lib.aa_model_blocked_virial(self._plan_handle, C.byref(g), cap, self._workspace.data_ptr(), self._workspace.numel(),
+                                                      out.data_ptr(), _stream_ptr(out)), "aa_model_blocked_virial")
+            return out.view(3, 3)
         lib.check(lib.lib.aa_model_virial(self._plan_handle, C.byref(g), self._workspace.data_ptr(), self._workspace.numel(),
                                           out.data_ptr(), _stream_ptr(out)), "aa_model_virial")
         return out.view(3, 3)
@@ -1174,7 +1300,13 @@ class HipAllegroModel(torch.nn.Module):
             raise RuntimeError("atom_virial reads what a step with forces left behind: call energy_forces first")
         out = torch.empty((graph.num_atoms, 3, 3), dtype=self.dtype, device=self._workspace.device)
         g = graph.c_struct()
+        cap = self._blocked_cap_for("atom_virial")
         with _device_ctx(out.device):
+            if cap is not None:  # the last step on this device was a blocked one
+                lib.check(lib.lib.aa_model_blocked_atom_virial(self._plan_handle, C.byref(g), cap, self._workspace.data_ptr(),
+                                                               self._workspace.numel(), self._ATOM_VIRIAL[attribution], out.data_ptr(),
+                                                               _stream_ptr(out)), "aa_model_blocked_atom_virial")
+                return out
             lib.check(lib.lib.aa_model_atom_virial(self._plan_handle, C.byref(g), self._workspace.data_ptr(), self._workspace.numel(),
                                                    self._ATOM_VIRIAL[attribution], out.data_ptr(), _stream_ptr(out)),
                       "aa_model_atom_virial")

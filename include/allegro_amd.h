@@ -413,6 +413,48 @@ enum { AA_ATOM_VIRIAL_CENTER = 0, AA_ATOM_VIRIAL_NEIGHBOR = 1, AA_ATOM_VIRIAL_SP
 int aa_model_atom_virial(const aa_model_plan* plan, const aa_graph* graph, void* workspace, size_t workspace_bytes,
                          int attribution, void* out_n9, aa_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 2b. Block-wise step: one frame, one center-atom block after the other, in ONE arena sized for the largest block.
+ *    Allegro is strictly local -- every per-edge quantity depends on the edges of its own center atom only -- so a contiguous
+ *    block of center atoms with the contiguous slice of its edges is an independent sub-problem: the results are those of
+ *    aa_model_energy_forces on the frame (same kernels, same per-atom sums), while the per-edge workspace (about 8 KB per edge)
+ *    is paid for max_block_edges instead of num_edges.  What stays frame-wide: two [E,4] arrays (32 B per edge in fp32), one
+ *    [N+1] int32 array and the per-atom parts of the arena.
+ *
+ *    graph        the WHOLE frame: absolute rowptr, center / nbr / shift_vec of all E edges, t_rowptr / t_perm and max_degree of the
+ *                 frame; atom_begin / atom_end are not read.
+ *    block_atoms  HOST [num_blocks + 1], non-decreasing, block_atoms[0] = 0, block_atoms[num_blocks] = num_atoms: block b owns
+ *                 the center atoms [block_atoms[b], block_atoms[b + 1]).
+ *    block_edges  HOST [num_blocks + 1]: block_edges[b] = rowptr[block_atoms[b]] (the host that built the list holds these
+ *                 values), so block b's edges are [block_edges[b], block_edges[b + 1]).
+ *    max_block_edges  the largest block_edges[b + 1] - block_edges[b].
+ *    Blocks without atoms or without edges are legal; their atoms still get their per-type shift energy.
+ *
+ *    Errors.  AA_ERR_INVALID with a message: block_atoms / block_edges that do not run from 0 to num_atoms / num_edges or decrease;
+ *    forces != NULL without t_rowptr / t_perm (forces are assembled ONCE over the frame, in the fixed order of the transposed CSR;
+ *    there is no atomics fallback); a plan with aa_model_plan_enable_graph or aa_model_plan_enable_taps on (the blocked step is
+ *    neither captured nor tapped).  AA_ERR_WORKSPACE: less than aa_model_blocked_workspace_bytes at the largest block.
+ *    A block_edges entry that is not the row pointer of its atom cannot be seen by the host; the device checks every cut.  A wrong one
+ *    raises the plan's status word and turns atom_energy and forces of the WHOLE frame into NaN in the same call (no kernel indexes
+ *    outside the frame's arrays because of it); the next call on the plan, or aa_model_check, returns AA_ERR_INVALID naming the block --
+ *    the contract of a broken atom_begin / atom_end hint.
+ *
+ *    atom_energy [N]: every entry is written exactly once, by its block.  forces [N,3] or NULL: written, bit-reproducible, in the
+ *    summation order of aa_model_energy_forces with a transposed CSR.  An energy-only call needs no frame-wide edge arrays and the
+ *    size function says so.  aa_model_plan_set_forward_events is ignored by this call (the blocks run one after the other on `stream`).
+ *    aa_model_blocked_virial / aa_model_blocked_atom_virial: aa_model_virial / aa_model_atom_virial (same attributions, same rules) for
+ *    the LAST blocked call with forces on this workspace, which they find through the same max_block_edges.
+ * ------------------------------------------------------------------------------------------ */
+size_t aa_model_blocked_workspace_bytes(const aa_model_plan* plan, int64_t num_atoms, int64_t num_edges, int64_t max_block_edges,
+                                        int with_forces);
+int aa_model_energy_forces_blocked(const aa_model_plan* plan, const void* dev_weights, const aa_graph* graph, const void* pos,
+                                   int32_t num_blocks, const int64_t* block_atoms, const int64_t* block_edges, void* workspace,
+                                   size_t workspace_bytes, void* atom_energy, void* forces, aa_stream stream);
+int aa_model_blocked_virial(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges, void* workspace,
+                            size_t workspace_bytes, void* virial9, aa_stream stream);
+int aa_model_blocked_atom_virial(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges, void* workspace,
+                                 size_t workspace_bytes, int attribution, void* out_n9, aa_stream stream);
+
 /* debug/parity taps: copy an intermediate of the LAST call out of the workspace layout.
  * name in {"edge_attrs","edge_embedding","edge_features","emb0","vec"}; a "+f" suffix selects the workspace layout of
  * a step that computed forces (required for "dvec": dE/dr_e [E,4]); returns elements per edge or <0 */
