@@ -247,6 +247,8 @@ class AllegroLib:
         L.aa_model_virial.restype = C.c_int
         L.aa_model_atom_virial.argtypes = [C.c_void_p, C.POINTER(Graph), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
         L.aa_model_atom_virial.restype = C.c_int
+        L.aa_model_heat_flux.argtypes = [C.c_void_p, C.POINTER(Graph), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.aa_model_heat_flux.restype = C.c_int
         _i64p = C.POINTER(C.c_int64)
         L.aa_model_blocked_workspace_bytes.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int]
         L.aa_model_blocked_workspace_bytes.restype = C.c_size_t
@@ -257,6 +259,8 @@ class AllegroLib:
         L.aa_model_blocked_virial.restype = C.c_int
         L.aa_model_blocked_atom_virial.argtypes = [C.c_void_p, C.POINTER(Graph), C.c_int64, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
         L.aa_model_blocked_atom_virial.restype = C.c_int
+        L.aa_model_blocked_heat_flux.argtypes = [C.c_void_p, C.POINTER(Graph), C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.aa_model_blocked_heat_flux.restype = C.c_int
         L.aa_nl_workspace_bytes.argtypes = [C.c_int64]
         L.aa_nl_workspace_bytes.restype = C.c_size_t
         L.aa_nl_count.argtypes = [C.POINTER(NlInput), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]

@@ -800,6 +800,19 @@ struct AtomVirialArgs {
 };
 template <typename T>
 int launch_atom_virial(const AtomVirialArgs& a, hipStream_t stream);
+// potential part of the heat flux: out[b] = -sum_e (r_e)_b (d[e] . vel[nbr[e]]), one stream over the edges (no transposed CSR),
+// reduced as launch_virial (double, fixed order, no atomics); the block partials take the first 3 * blocks doubles of VirialArgs' scratch
+struct HeatFluxArgs {
+  int64_t E;
+  const void* dvec;    // [E,4]
+  const void* vec;     // [E,4] unit vector, length
+  const int32_t* nbr;  // [E]
+  const void* vel;     // [N,3] model dtype (ghost rows are the caller's)
+  double* partial;     // [kVirialBlocks][3] scratch
+  void* out;           // [3] model dtype
+};
+template <typename T>
+int launch_heat_flux(const HeatFluxArgs& a, hipStream_t stream);
 // verifies the aa_graph.atom_begin / atom_end promise (no edge segment outside the block): *status = -2 otherwise
 int launch_graph_hint_check(const int32_t* rowptr, int64_t N, int64_t a0, int64_t a1, int32_t* status, void* atom_energy, void* forces,
                             int esize, hipStream_t stream);

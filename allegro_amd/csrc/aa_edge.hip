@@ -769,6 +769,54 @@ int launch_virial(const VirialArgs& a, hipStream_t stream) {
   return AA_OK;
 }
 
+// potential part of the heat flux: one stream over the two [E,4] arrays (rows loaded whole, as atom_virial_edge) plus the gathered
+// velocity of the edge's neighbor; per-block partial sums in double (fixed order), then one block adds the partials and negates
+template <typename T>
+__global__ __launch_bounds__(256) void heat_flux_partial_kernel(HeatFluxArgs a) {
+  typedef T V4 __attribute__((ext_vector_type(4)));
+  double* sP = reinterpret_cast<double*>(aa_smem);  // [256][3]
+  double jx = 0.0, jy = 0.0, jz = 0.0;
+  const T* dv = static_cast<const T*>(a.dvec);
+  const T* vc = static_cast<const T*>(a.vec);
+  const T* vel = static_cast<const T*>(a.vel);
+  for (int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x; e < a.E; e += int64_t(gridDim.x) * 256) {
+    const V4 d = *reinterpret_cast<const V4*>(dv + 4 * e);
+    const V4 v = *reinterpret_cast<const V4*>(vc + 4 * e);
+    const T* u = vel + 3 * int64_t(a.nbr[e]);
+    const double p = double(d[0]) * double(u[0]) + double(d[1]) * double(u[1]) + double(d[2]) * double(u[2]);  // g_e . v_j(e)
+    const double r = double(v[3]);
+    jx += double(v[0]) * r * p;
+    jy += double(v[1]) * r * p;
+    jz += double(v[2]) * r * p;
+  }
+  sP[threadIdx.x * 3] = jx;
+  sP[threadIdx.x * 3 + 1] = jy;
+  sP[threadIdx.x * 3 + 2] = jz;
+  __syncthreads();
+  for (int st = 128; st >= 1; st >>= 1) {
+    if (int(threadIdx.x) < st)
+      for (int k = 0; k < 3; ++k) sP[threadIdx.x * 3 + k] += sP[(threadIdx.x + st) * 3 + k];
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) a.partial[blockIdx.x * 3 + threadIdx.x] = sP[threadIdx.x];
+}
+template <typename T>
+__global__ __launch_bounds__(64) void heat_flux_final_kernel(HeatFluxArgs a, int nblocks) {
+  if (threadIdx.x < 3) {
+    double s = 0.0;
+    for (int b2 = 0; b2 < nblocks; ++b2) s += a.partial[b2 * 3 + threadIdx.x];
+    static_cast<T*>(a.out)[threadIdx.x] = T(0.0 - s);  // (an empty list gives +0)
+  }
+}
+template <typename T>
+int launch_heat_flux(const HeatFluxArgs& a, hipStream_t stream) {
+  const int nb = int(std::min<int64_t>(kVirialBlocks, std::max<int64_t>(1, (a.E + 255) / 256)));
+  hipLaunchKernelGGL(heat_flux_partial_kernel<T>, dim3(nb), dim3(256), sizeof(double) * 256 * 3, stream, a);
+  hipLaunchKernelGGL(heat_flux_final_kernel<T>, dim3(1), dim3(64), 0, stream, a, nb);
+  AA_CHECK_HIP(hipGetLastError());
+  return AA_OK;
+}
+
 template <typename T>
 int launch_force_gather(const ForceGatherArgs& a, hipStream_t stream) {
   if (a.N == 0) return AA_OK;
@@ -873,6 +921,7 @@ int launch_readout_backward(const ReadoutArgs& a, hipStream_t stream) {
   template int launch_force_gather<T>(const ForceGatherArgs&, hipStream_t);    \
   template int launch_virial<T>(const VirialArgs&, hipStream_t);               \
   template int launch_atom_virial<T>(const AtomVirialArgs&, hipStream_t);      \
+  template int launch_heat_flux<T>(const HeatFluxArgs&, hipStream_t);          \
   template int launch_pair_zbl<T>(const PairZblArgs&, hipStream_t);            \
   template int launch_readout_reduce<T>(const ReadoutArgs&, hipStream_t);      \
   template int launch_readout_backward<T>(const ReadoutArgs&, hipStream_t);

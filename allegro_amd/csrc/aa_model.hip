@@ -3055,6 +3055,28 @@ extern "C" int aa_model_atom_virial(const aa_model_plan* plan, const aa_graph* g
   return plan->cfg.dtype == AA_F32 ? launch_atom_virial<float>(a, s) : launch_atom_virial<double>(a, s);
 }
 
+namespace {
+// shared by aa_model_heat_flux and its blocked twin: the argument checks and the launch pair, on the two [E,4] arrays at `dvec` / `vec`
+int heat_flux_from(const aa_model_plan* plan, const aa_graph* graph, const char* who, char* dvec, char* vec, char* vir_part,
+                   const void* velocities, void* flux3, aa_stream stream) {
+  if (!flux3) return fail(AA_ERR_INVALID, std::string(who) + ": null flux3");
+  if (!velocities && graph->num_atoms > 0) return fail(AA_ERR_INVALID, std::string(who) + ": null velocities");
+  if (graph->num_edges > 0 && !graph->nbr) return fail(AA_ERR_INVALID, std::string(who) + ": null neighbor array (aa_graph.nbr)");
+  HeatFluxArgs a{graph->num_edges, dvec, vec, graph->nbr, velocities, reinterpret_cast<double*>(vir_part), flux3};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return plan->cfg.dtype == AA_F32 ? launch_heat_flux<float>(a, s) : launch_heat_flux<double>(a, s);
+}
+}  // namespace
+
+extern "C" int aa_model_heat_flux(const aa_model_plan* plan, const aa_graph* graph, void* workspace, size_t workspace_bytes,
+                                  const void* velocities, void* flux3, aa_stream stream) {
+  AA_REQUIRE(plan && graph && workspace, "aa_model_heat_flux: null argument");
+  const Workspace w = layout_workspace(plan, graph->num_atoms, graph->num_edges, 1);
+  if (w.total > workspace_bytes) return fail(AA_ERR_WORKSPACE, "aa_model_heat_flux: workspace too small (was it sized with forces?)");
+  char* base = static_cast<char*>(workspace);
+  return heat_flux_from(plan, graph, "aa_model_heat_flux", base + w.dvec, base + w.vec, base + w.vir_part, velocities, flux3, stream);
+}
+
 // ------------------------------------------------------------------------------------------------
 // blocked step: the frame one block of center atoms after the other, in one arena
 // ------------------------------------------------------------------------------------------------
@@ -3181,6 +3203,18 @@ extern "C" int aa_model_blocked_atom_virial(const aa_model_plan* plan, const aa_
   AtomVirialArgs a{graph->num_atoms, graph->rowptr, graph->t_rowptr, graph->t_perm, base + bw.dvec, base + bw.vec, cc, cn, out_n9};
   hipStream_t s = static_cast<hipStream_t>(stream);
   return plan->cfg.dtype == AA_F32 ? launch_atom_virial<float>(a, s) : launch_atom_virial<double>(a, s);
+}
+
+extern "C" int aa_model_blocked_heat_flux(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges, void* workspace,
+                                          size_t workspace_bytes, const void* velocities, void* flux3, aa_stream stream) {
+  AA_REQUIRE(plan && graph && workspace, "aa_model_blocked_heat_flux: null argument");
+  AA_REQUIRE(max_block_edges >= 0, "aa_model_blocked_heat_flux: negative max_block_edges");
+  const BlockedWorkspace bw = layout_blocked(plan, graph->num_atoms, graph->num_edges, std::min(max_block_edges, graph->num_edges), 1);
+  if (bw.total > workspace_bytes)
+    return fail(AA_ERR_WORKSPACE, "aa_model_blocked_heat_flux: workspace too small (was it sized with forces, at this max_block_edges?)");
+  char* base = static_cast<char*>(workspace);
+  return heat_flux_from(plan, graph, "aa_model_blocked_heat_flux", base + bw.dvec, base + bw.vec, base + bw.arena.vir_part, velocities, flux3,
+                        stream);
 }
 
 extern "C" int aa_model_debug_tap(const aa_model_plan* plan, const char* name, int64_t N, int64_t E, const void* workspace,

@@ -11,7 +11,9 @@ when the backend is "nccl") of the [N,3] force array per step.  The reference ha
 `HaloShard` + `energy_forces_halo` (below, round 4) are the sharded-integrator form of the same decomposition -- what LAMMPS
 itself does around pair_allegro: every rank keeps only ITS atoms' positions, ghost positions arrive by forward
 communication and ghost forces leave by reverse communication (two `all_to_all_single` of the ghost rows only, sizes fixed
-per neighbour list), energies stay local; nothing O(N) exists on a rank.  `bench.py --gpus N` times that path.
+per neighbour list), energies stay local; nothing O(N) exists on a rank.  `bench.py --gpus N` times that path.  On request the same
+call returns the frame's strain derivative and potential heat flux (one all-reduce of 9 + 3 numbers) and the per-atom virial of the
+owned atoms (ghost rows [n_ghost,9] sent home like the ghost forces); `LocalShard` and `energy_forces_sharded` have no such outputs.
 
 Two earlier layouts of a rank's share: `LocalShard` (compact local numbering: owned block + ghost atoms, everything the
 rank holds is O(local); what bench.py --gpus N runs) and `local_graph` (global numbering with the owned-range hint;
@@ -250,11 +252,23 @@ class HaloShard:
         return pos_loc, send_f, recv_r
 
     def accumulate_reverse(self, f_own: torch.Tensor, recv_r: torch.Tensor):
-        """Step phase 3: adds the force rows received for owned atoms (`recv_r[:ns]`, row ns stays zero) in a fixed order
-        (touched ids are unique: one add per row, fixed order inside the gathered sum)."""
+        """Step phase 3: adds the rows received for owned atoms (`recv_r[:ns]`, row ns stays zero) in a fixed order (touched ids
+        are unique: one add per row, fixed order inside the gathered sum).  Any row width: force rows `[., 3]` into `[n_own, 3]`,
+        per-atom virial rows `[., 9]` into `[n_own, 9]`."""
         if self._rows is not None:
             f_own.index_add_(0, self._touched, recv_r[self._rows].sum(1))
         return f_own
+
+    def pack_velocities(self, vel_own: torch.Tensor):
+        """Forward phase of the heat flux: owned velocities into the local array, the rows other ranks hold as ghosts into a send
+        buffer of their own (the positions' plan: `send_idx`).  Returns (vel_loc [n_own + n_ghost, 3], send rows [ns, 3])."""
+        if tuple(vel_own.shape) != (self.n_own, 3):
+            raise ValueError(f"velocities_own must be [{self.n_own}, 3], not {list(vel_own.shape)} (slab order: shard.owned_ids())")
+        vel_loc, send_v = self._velocity_buffers(vel_own.dtype, vel_own.device)
+        vel_loc[:self.n_own] = vel_own
+        if self.send_idx.numel():
+            torch.index_select(vel_own, 0, self.send_idx, out=send_v)
+        return vel_loc, send_v
 
     # -- construction ------------------------------------------------------------------------------------------------
     @classmethod
@@ -428,28 +442,118 @@ class HaloShard:
             self._bufs = (torch.empty((self.n_own + self.n_ghost, 3), dtype=dtype, device=device),  # local positions
                           torch.empty((ns, 3), dtype=dtype, device=device),                            # rows sent forward
                           torch.zeros((ns + 1, 3), dtype=dtype, device=device))                        # rows received in reverse (+ zero row)
+            self._wide = {}
         return self._bufs
 
+    def reverse_buffer(self, width: int, dtype, device) -> torch.Tensor:
+        """Persistent receive rows of a reverse communication of `width` numbers per row, `[ns + 1, width]` (row ns stays zero):
+        the force rows of `_buffers` at width 3, one more buffer per other width (9: per-atom virial rows), allocated on first use."""
+        bufs = self._buffers(dtype, device)
+        if width == 3:
+            return bufs[2]
+        if width not in self._wide:
+            self._wide[width] = torch.zeros((int(self.send_idx.numel()) + 1, width), dtype=dtype, device=device)
+        return self._wide[width]
 
-def energy_forces_halo(model, pos_own: torch.Tensor, shard: HaloShard):
+    def _velocity_buffers(self, dtype, device):
+        if self._bufs is None:
+            self._buffers(dtype, device)
+        if ("vel", dtype) not in self._wide:
+            self._wide[("vel", dtype)] = (torch.empty((self.n_own + self.n_ghost, 3), dtype=dtype, device=device),  # local velocities
+                                          torch.empty((int(self.send_idx.numel()), 3), dtype=dtype, device=device))  # rows sent forward
+        return self._wide[("vel", dtype)]
+
+
+_ATTRIBUTIONS = ("center", "neighbor", "split")
+
+
+def _check_observables(atom_virial):
+    if atom_virial is not None and atom_virial not in _ATTRIBUTIONS:
+        raise ValueError(f"atom_virial must be None or one of {list(_ATTRIBUTIONS)}, not {atom_virial!r}")
+
+
+def _shard_observables(model, shard: HaloShard, virial: bool, atom_virial, vel_loc):
+    """What one shard contributes, read off the step that has JUST run on `shard.graph` (the model's workspace still holds it):
+    (sums, w).  `sums`: float64 [9 if virial] + [3 if vel_loc is given], this shard's part of dE/d(strain) and of the potential
+    heat flux -- a shard's edges are those of its owned centers, so the parts add up over the ranks; None when neither is asked for.
+    `w`: the local per-atom virial [n_own + n_ghost, 9] (owned rows first) or None."""
+    parts = []
+    if virial:
+        parts.append(model.virial(shard.graph).reshape(9).double())
+    if vel_loc is not None:
+        parts.append(model.heat_flux_potential(shard.graph, vel_loc).double())
+    sums = torch.cat(parts) if parts else None
+    w = model.atom_virial(shard.graph, atom_virial).reshape(-1, 9) if atom_virial is not None else None
+    return sums, w
+
+
+def _unpack_sums(obs: dict, sums: torch.Tensor, virial: bool, flux: bool, dtype):
+    o = 0
+    if virial:
+        obs["virial"] = sums[:9].to(dtype, copy=True).reshape(3, 3)
+        o = 9
+    if flux:
+        obs["heat_flux"] = sums[o:o + 3].to(dtype, copy=True)
+
+
+def energy_forces_halo(model, pos_own: torch.Tensor, shard: HaloShard, *, virial: bool = False, atom_virial: Optional[str] = None,
+                       velocities_own: Optional[torch.Tensor] = None):
     """One step of a sharded MD code on this rank: forward communication (ghost positions), the hot path on the compact local
     arrays, reverse communication (ghost forces).  `pos_own` [n_own,3]: the positions of the rank's OWN atoms (slab order).
     Returns (E_i [n_own], forces [n_own,3]) of the owned atoms, complete (every contribution of every rank included).
-    Collectives per step: two `all_to_all_single` (RCCL over xGMI with backend "nccl"), ghost rows only; none with one rank."""
+    Collectives per step: two `all_to_all_single` (RCCL over xGMI with backend "nccl"), ghost rows only; none with one rank.
+
+    With an observable requested the return is (E_i, forces, obs), `obs` a dict of what was asked for:
+      virial=True            obs["virial"] [3,3]: dE/d(strain) of the WHOLE frame (stress = virial / volume), the same on every rank;
+      atom_virial=...        obs["atom_virial"] [n_own,3,3] of the owned atoms, complete: "center" is local (no communication);
+                             "neighbor" / "split" send the ghost rows [n_ghost,9] home with one more reverse `all_to_all_single` on
+                             the plan of the forces and add them in the same fixed order;
+      velocities_own=[n_own,3]  obs["heat_flux"] [3]: potential part of the Green-Kubo heat flux of the WHOLE frame, the same on every
+                             rank: ghost velocities travel forward like ghost positions (one more `all_to_all_single`), every rank
+                             streams its own edges once (`heat_flux_potential` on the local graph).
+    `virial` and `heat_flux` are summed over the ranks by ONE `all_reduce` of their 9 + 3 numbers together, carried in float64."""
     import torch.distributed as dist
 
+    _check_observables(atom_virial)
+    want_flux = velocities_own is not None
     pos_loc, send_f, recv_r = shard.pack_forward(pos_own)
     n_own = shard.n_own
     multi = shard.connected
     if multi:
         _all_to_all_rows(pos_loc[n_own:], send_f, shard.recv_counts, shard.send_counts, shard.group, shard.host_staged)
+    vel_loc = None
+    if want_flux:
+        vel_loc, send_v = shard.pack_velocities(velocities_own)
+        if multi:
+            _all_to_all_rows(vel_loc[n_own:], send_v, shard.recv_counts, shard.send_counts, shard.group, shard.host_staged)
     e_loc, f_loc = model.energy_forces(pos_loc, shard.graph)
     f_own = f_loc[:n_own]
     if multi:
         ns = recv_r.shape[0] - 1
         _all_to_all_rows(recv_r[:ns], f_loc[n_own:].contiguous(), shard.send_counts, shard.recv_counts, shard.group, shard.host_staged)
         shard.accumulate_reverse(f_own, recv_r)
-    return e_loc[:n_own], f_own
+    if not (virial or want_flux or atom_virial is not None):
+        return e_loc[:n_own], f_own
+    obs = {}
+    sums, w = _shard_observables(model, shard, virial, atom_virial, vel_loc)
+    if w is not None:
+        w_own = w[:n_own]
+        if multi and atom_virial != "center":
+            recv_w = shard.reverse_buffer(9, w.dtype, w.device)
+            _all_to_all_rows(recv_w[:recv_w.shape[0] - 1], w[n_own:].contiguous(), shard.send_counts, shard.recv_counts, shard.group,
+                             shard.host_staged)
+            shard.accumulate_reverse(w_own, recv_w)
+        obs["atom_virial"] = w_own.reshape(n_own, 3, 3)
+    if sums is not None:
+        if multi:
+            if shard.host_staged:
+                sums_h = sums.cpu()
+                dist.all_reduce(sums_h, group=shard.group)
+                sums = sums_h.to(sums.device)
+            else:
+                dist.all_reduce(sums, group=shard.group)
+        _unpack_sums(obs, sums, virial, want_flux, pos_own.dtype)
+    return e_loc[:n_own], f_own, obs
 
 
 def _all_to_all_rows(out: torch.Tensor, inp: torch.Tensor, out_splits, in_splits, group, host_staged: bool):
@@ -505,18 +609,48 @@ class InProcessHaloGroup:
                 o += n
             assert o == outs[q].shape[0]
 
-    def step(self, model, pos_own_list):
-        """One step of every rank: [(E_i [n_own], forces [n_own, 3])] in rank order (complete, reverse communication included)."""
+    def step(self, model, pos_own_list, *, virial: bool = False, atom_virial: Optional[str] = None, velocities_own_list=None):
+        """One step of every rank: [(E_i [n_own], forces [n_own, 3])] in rank order (complete, reverse communication included).
+        With an observable requested (the keywords of `energy_forces_halo`; `velocities_own_list`: one [n_own,3] per rank) every
+        entry is (E_i, forces, obs): the third reverse exchange is a slice copy like the other two, the all-reduce a sum in rank order."""
+        _check_observables(atom_virial)
+        want_flux = velocities_own_list is not None
+        want_obs = virial or want_flux or atom_virial is not None
         packed = [s.pack_forward(p) for s, p in zip(self.shards, pos_own_list)]
         self._exchange([pk[0][s.n_own:] for pk, s in zip(packed, self.shards)], [pk[1] for pk in packed], forward=True)
-        res = []
-        for s, pk in zip(self.shards, packed):
+        vels = [None] * len(self.shards)
+        if want_flux:
+            vpk = [s.pack_velocities(v) for s, v in zip(self.shards, velocities_own_list)]
+            self._exchange([vp[0][s.n_own:] for vp, s in zip(vpk, self.shards)], [vp[1] for vp in vpk], forward=True)
+            vels = [vp[0] for vp in vpk]
+        res, local = [], []
+        for s, pk, vel_loc in zip(self.shards, packed, vels):
             e_loc, f_loc = model.energy_forces(pk[0], s.graph)
             res.append((e_loc.clone(), f_loc.clone()))  # (the model's output buffers are reused by the next shard's step)
+            if want_obs:  # (and so is its workspace: this shard's observables are read before the next shard's step)
+                local.append(_shard_observables(model, s, virial, atom_virial, vel_loc))
         self._exchange([pk[2][:pk[2].shape[0] - 1] for pk in packed], [f[s.n_own:] for (_, f), s in zip(res, self.shards)], forward=False)
         out = []
         for s, pk, (e_loc, f_loc) in zip(self.shards, packed, res):
             f_own = f_loc[:s.n_own]
             s.accumulate_reverse(f_own, pk[2])
             out.append((e_loc[:s.n_own], f_own))
-        return out
+        if not want_obs:
+            return out
+        obs = [{} for _ in self.shards]
+        if atom_virial is not None:
+            ws = [w for _, w in local]
+            if atom_virial != "center":
+                recv = [s.reverse_buffer(9, w.dtype, w.device) for s, w in zip(self.shards, ws)]
+                self._exchange([r[:r.shape[0] - 1] for r in recv], [w[s.n_own:] for w, s in zip(ws, self.shards)], forward=False)
+                for s, w, r in zip(self.shards, ws, recv):
+                    s.accumulate_reverse(w[:s.n_own], r)
+            for o, s, w in zip(obs, self.shards, ws):
+                o["atom_virial"] = w[:s.n_own].reshape(s.n_own, 3, 3)
+        if virial or want_flux:
+            total = local[0][0].clone()
+            for sums, _ in local[1:]:
+                total += sums
+            for o, (e_own, _) in zip(obs, out):
+                _unpack_sums(o, total, virial, want_flux, e_own.dtype)
+        return [(e, f, o) for (e, f), o in zip(out, obs)]

@@ -1315,11 +1315,26 @@ class HipAllegroModel(torch.nn.Module):
     def heat_flux_potential(self, graph: PreparedGraph, velocities: torch.Tensor) -> torch.Tensor:
         """Potential part of the Green-Kubo heat flux [3] of the last step with forces on `graph`:
         J_pot[b] = -sum_e (r_e)_b (dE/dr_e . v_j(e)) = -sum_n sum_a v_n[a] Wn_n[a][b], Wn = atom_virial(graph, "neighbor").
-        `velocities`: [N,3] (ghost rows carry the velocity of their source atom).  The convective part sum_n E_n v_n is the caller's."""
+        `velocities`: [N,3] (ghost rows carry the velocity of their source atom).  The convective part sum_n E_n v_n is the caller's.
+        One streaming reduction over the edges (`aa_model_heat_flux`): bit-reproducible, and the graph needs no transposed CSR."""
         if tuple(velocities.shape) != (graph.num_atoms, 3):
             raise ValueError(f"velocities must be [{graph.num_atoms}, 3], not {list(velocities.shape)}")
-        wn = self.atom_virial(graph, "neighbor")
-        return -torch.einsum("na,nab->b", velocities.to(wn), wn)
+        lib = self._get_lib()
+        if getattr(self, "_plan_handle", None) is None or self._workspace is None:
+            raise RuntimeError("heat_flux_potential reads what a step with forces left behind: call energy_forces first")
+        vel = velocities.detach().to(device=self._workspace.device, dtype=self.dtype).contiguous()
+        out = torch.empty(3, dtype=self.dtype, device=self._workspace.device)
+        g = graph.c_struct()
+        cap = self._blocked_cap_for("heat_flux_potential")
+        with _device_ctx(out.device):
+            if cap is not None:  # the last step on this device was a blocked one
+                lib.check(lib.lib.aa_model_blocked_heat_flux(self._plan_handle, C.byref(g), cap, self._workspace.data_ptr(),
+                                                             self._workspace.numel(), vel.data_ptr(), out.data_ptr(), _stream_ptr(out)),
+                          "aa_model_blocked_heat_flux")
+                return out
+            lib.check(lib.lib.aa_model_heat_flux(self._plan_handle, C.byref(g), self._workspace.data_ptr(), self._workspace.numel(),
+                                                 vel.data_ptr(), out.data_ptr(), _stream_ptr(out)), "aa_model_heat_flux")
+        return out
 
     def enable_hip_graph(self, on: bool = True) -> None:
         """Capture the step's launch sequence into a hipGraph and replay it (aa_model_plan_enable_graph): for

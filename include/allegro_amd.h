@@ -413,6 +413,20 @@ enum { AA_ATOM_VIRIAL_CENTER = 0, AA_ATOM_VIRIAL_NEIGHBOR = 1, AA_ATOM_VIRIAL_SP
 int aa_model_atom_virial(const aa_model_plan* plan, const aa_graph* graph, void* workspace, size_t workspace_bytes,
                          int attribution, void* out_n9, aa_stream stream);
 
+/* Potential part of the Green-Kubo heat flux of the whole frame, straight from the same two per-edge buffers (call it after a
+ * step with forces, like aa_model_virial; the same workspace check):
+ *   J_pot[b] = -sum_e (r_e)_b (g_e . v_{j(e)})      (= -sum_n sum_a v_n[a] Wn_n[a][b] with Wn of AA_ATOM_VIRIAL_NEIGHBOR)
+ * velocities: [num_atoms, 3], model dtype, device memory; ghost rows (pair_allegro layout) carry the velocity of their source atom --
+ * they are the caller's.  flux3: [3], model dtype, device memory.  The convective part sum_n E_n v_n stays with the caller.
+ * One stream over the edges in list order: reads aa_graph.nbr, does NOT need t_rowptr / t_perm.  Sums run in double in a fixed order
+ * without atomics: the result is bit-reproducible.  num_edges == 0 writes zeros; with num_atoms == 0 velocities may be NULL.
+ * AA_ERR_INVALID: NULL velocities (with atoms) or NULL flux3; AA_ERR_WORKSPACE: a workspace not sized for a step with forces; a refused
+ * call writes nothing.  A launch pair of its own: not part of the step, of its captured graph or of its profile.  Its block partials
+ * live in the scratch of aa_model_virial inside `workspace` (the workspace size is unchanged): like every call on a workspace,
+ * it belongs on that workspace's one stream, and may not overlap aa_model_virial on another. */
+int aa_model_heat_flux(const aa_model_plan* plan, const aa_graph* graph, void* workspace, size_t workspace_bytes,
+                       const void* velocities, void* flux3, aa_stream stream);
+
 /* ------------------------------------------------------------------------------------------
  * 2b. Block-wise step: one frame, one center-atom block after the other, in ONE arena sized for the largest block.
  *    Allegro is strictly local -- every per-edge quantity depends on the edges of its own center atom only -- so a contiguous
@@ -444,6 +458,7 @@ int aa_model_atom_virial(const aa_model_plan* plan, const aa_graph* graph, void*
  *    size function says so.  aa_model_plan_set_forward_events is ignored by this call (the blocks run one after the other on `stream`).
  *    aa_model_blocked_virial / aa_model_blocked_atom_virial: aa_model_virial / aa_model_atom_virial (same attributions, same rules) for
  *    the LAST blocked call with forces on this workspace, which they find through the same max_block_edges.
+ *    aa_model_blocked_heat_flux: aa_model_heat_flux (same arguments, same rules, no transposed CSR) for that call, found the same way.
  * ------------------------------------------------------------------------------------------ */
 size_t aa_model_blocked_workspace_bytes(const aa_model_plan* plan, int64_t num_atoms, int64_t num_edges, int64_t max_block_edges,
                                         int with_forces);
@@ -454,6 +469,8 @@ int aa_model_blocked_virial(const aa_model_plan* plan, const aa_graph* graph, in
                             size_t workspace_bytes, void* virial9, aa_stream stream);
 int aa_model_blocked_atom_virial(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges, void* workspace,
                                  size_t workspace_bytes, int attribution, void* out_n9, aa_stream stream);
+int aa_model_blocked_heat_flux(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges, void* workspace,
+                               size_t workspace_bytes, const void* velocities, void* flux3, aa_stream stream);
 
 /* debug/parity taps: copy an intermediate of the LAST call out of the workspace layout.
  * name in {"edge_attrs","edge_embedding","edge_features","emb0","vec"}; a "+f" suffix selects the workspace layout of
