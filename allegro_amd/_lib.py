@@ -148,6 +148,12 @@ class PruneInput(C.Structure):
                 ("rowptr", C.c_void_p), ("nbr", C.c_void_p), ("shift_vec", C.c_void_p)]
 
 
+class EdgeList(C.Structure):
+    """`aa_edge_list`: the caller's edge_index (+ shift vectors, + positions for pruning) as aa_graph_build_* read it."""
+    _fields_ = [("num_atoms", C.c_int64), ("num_edges", C.c_int64), ("edge_index", C.c_void_p), ("row_stride", C.c_int64),
+                ("index_is_int64", C.c_int32), ("dtype", C.c_int32), ("pos", C.c_void_p), ("shift_vec", C.c_void_p)]
+
+
 class AllegroLib:
     def __init__(self, cdll: C.CDLL, is_emulation: bool = False):
         self.lib = cdll
@@ -284,6 +290,14 @@ class AllegroLib:
         L.aa_graph_prune_fill.argtypes = [C.POINTER(PruneInput), C.POINTER(NlTypes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.aa_graph_prune_fill.restype = C.c_int
+        L.aa_graph_build_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+        L.aa_graph_build_workspace_bytes.restype = C.c_size_t
+        L.aa_graph_build_count.argtypes = [C.POINTER(EdgeList), C.POINTER(NlTypes), C.c_void_p, C.c_size_t, C.c_void_p,
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
+        L.aa_graph_build_count.restype = C.c_int
+        L.aa_graph_build_fill.argtypes = [C.POINTER(EdgeList), C.POINTER(NlTypes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.aa_graph_build_fill.restype = C.c_int
         L.aa_model_weights_bytes.argtypes = [C.c_void_p]
         L.aa_model_weights_bytes.restype = C.c_size_t
         L.aa_model_plan_layout_hash.argtypes = [C.c_void_p]

@@ -381,10 +381,8 @@ __global__ __launch_bounds__(256) void gt_place_kernel(const int32_t* nbr, int64
 // one wave per atom: every entry's final position is its RANK inside the group (edge ids are distinct), counted with wave shuffles
 // from registers -- no data-dependent loop over memory, whatever order the atomics left the group in (groups of more than 256
 // entries: one lane sorts in place)
-__global__ __launch_bounds__(256) void gt_sort_kernel(int64_t N, const int32_t* t_rowptr, int32_t* t_perm) {
-  const int lane = threadIdx.x & 63;
-  const int64_t a = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
-  if (a >= N) return;
+// (the body is a device function so that the list ingest, aa_graph_build_fill, ranks its center segments with the same code)
+__device__ __forceinline__ void gt_sort_group(int lane, int64_t a, const int32_t* t_rowptr, int32_t* t_perm) {
   const int lo = __builtin_amdgcn_readfirstlane(t_rowptr[a]), d = __builtin_amdgcn_readfirstlane(t_rowptr[a + 1]) - lo;
   if (d <= 1) return;
   if (d > 256) {
@@ -423,6 +421,11 @@ __global__ __launch_bounds__(256) void gt_sort_kernel(int64_t N, const int32_t* 
 #pragma unroll
   for (int k = 0; k < 4; ++k)
     if (lane + 64 * k < d) t_perm[lo + rank[k]] = x[k];
+}
+__global__ __launch_bounds__(256) void gt_sort_kernel(int64_t N, const int32_t* t_rowptr, int32_t* t_perm) {
+  const int64_t a = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (a >= N) return;
+  gt_sort_group(threadIdx.x & 63, a, t_rowptr, t_perm);
 }
 // hints[0..2] = first atom with edges, one past the last atom with edges, largest segment (0, 0, 0 without edges)
 __global__ __launch_bounds__(256) void gt_hints_kernel(int64_t N, const int32_t* rowptr, int32_t* hints) {
@@ -851,6 +854,309 @@ extern "C" int aa_graph_transpose(int64_t num_atoms, int64_t num_edges, const in
     hipLaunchKernelGGL(gt_sort_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, N, t_rowptr, t_perm);
   }
   if (hints3) hipLaunchKernelGGL(gt_hints_kernel, dim3(1), dim3(256), 3 * 256 * sizeof(int), s, N, rowptr, hints3);
+  AA_CHECK_HIP(hipGetLastError());
+  return AA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// aa_graph_build_*: the aa_graph of the list a host actually has -- edge_index [2,E], int64 or int32, rows a stride apart, edges
+// in ANY order -- optionally reduced to the per-type-pair cutoffs on the way: center-sorted int32 CSR in stable order (ascending
+// input edge id inside a segment), perm, shift vectors, the transposed CSR and the three hints.
+//   count  one thread per input edge reads its center and neighbour (consecutive lanes, consecutive 8- or 4-byte elements: one
+//          coalesced stream per row), raises the range flags and the sortedness flag (center[e-1] > center[e]; the line is the
+//          lane's own or its neighbour's), evaluates prune_keeps -- the predicate of aa_graph_prune_*, the same function -- and
+//          adds to the center histogram.  Lanes that hold the same center in a row (all of them in a sorted list) merge into ONE
+//          integer atomic per run: the run length comes from six shuffle-doubling steps.  Counts do not depend on arrival order.
+//          Then nl_scan_* -> out_rowptr, gt_hints_kernel -> hints, and with `types` a scan of the keep flags over the edges.
+//   fill   reads the flags on the device (no host read).  Sorted input: output position = prefix sum of the keep flags (= e
+//          without `types`), the edge is emitted where it stands.  Unsorted input: counting-sort placement by an atomic cursor,
+//          then every center segment is RANKED by gt_sort_group (the code of gt_sort_kernel, serial branch beyond 256 entries),
+//          so no atomic decides a final position; a gather pass then emits center / nbr / shift_vec / perm through perm.  The
+//          emit also counts the neighbour histogram; nl_scan_* + a placement pass + gt_sort_kernel give t_rowptr / t_perm.
+// A raised range flag makes every fill kernel return before it touches an output.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+enum { kResUnsorted = 0, kResBadCenter = 1, kResBadNbr = 2, kResBadType = 3, kResHints = 4, kResInts = 16 };
+
+struct BuildDev {
+  int64_t N, E, stride;
+  const void* rows;       // edge_index: centers at [0, E), neighbours at [stride, stride + E)
+  const void* shift_vec;  // [E,3] in input order, or nullptr
+  int* a0;                // [N+1] workspace: center histogram (count), placement cursor (fill)
+  int* a1;                // [N+1] workspace: neighbour histogram
+  int* a2;                // [N+1] workspace: placement cursor of the transposition
+  int* scan_tmp;          // [max(N, E) / 4096 + 2]
+  int* res;               // [16] flags (0 unsorted, 1 / 2 bad center / neighbour: edge id + 1, 3 bad type) and hints [4..6]
+  int* permw;             // [E] input ids in output order while they are ranked: the caller's perm, or workspace
+  int* keepf;             // [E] workspace, typed only: 1 = the edge is kept
+  int* kpos;              // [E+1] workspace, typed only: exclusive prefix sums of keepf
+  PruneDev p;             // what prune_keeps reads: N, pos, shift_vec, atom_types, T, rc2, bad_type
+};
+struct BuildOut {
+  int32_t *center, *nbr, *perm;
+  void* shift_vec;
+  int transposed;
+};
+
+template <typename IT, typename T, typename TT, bool TYPED>
+__global__ __launch_bounds__(256) void gb_count_kernel(BuildDev b) {
+  const int lane = threadIdx.x & 63;
+  const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  int key = -1;  // the center this lane counts for; -1: nothing (every lane takes part in the exchanges below)
+  if (e < b.E) {
+    const IT* r0 = static_cast<const IT*>(b.rows);
+    const int64_t c = int64_t(r0[e]), j = int64_t(r0[b.stride + e]);
+    if (e > 0 && int64_t(r0[e - 1]) > c) b.res[kResUnsorted] = 1;
+    const bool okc = c >= 0 && c < b.N, okj = j >= 0 && j < b.N;
+    if (!okc) b.res[kResBadCenter] = int(e) + 1;
+    if (!okj) b.res[kResBadNbr] = int(e) + 1;
+    bool keep = okc && okj;
+    if constexpr (TYPED) {
+      if (keep) {
+        const T* pi = static_cast<const T*>(b.p.pos) + 3 * c;
+        const double* row = b.p.rc2 + clamped_type<TT>(b.p.atom_types, c, b.p.T, b.p.bad_type) * b.p.T;
+        keep = prune_keeps<T, TT>(b.p, e, int(j), double(pi[0]), double(pi[1]), double(pi[2]), row);
+      }
+      b.keepf[e] = keep ? 1 : 0;
+    }
+    if (keep) key = int(c);
+  }
+  // len = how many lanes from this one on hold the same key without a gap, min(run, 2 st) after the step of width st
+  int len = 1;
+  for (int st = 1; st < 64; st <<= 1) {
+    const int okey = __shfl_down(key, st), olen = __shfl_down(len, st);
+    if (len == st && lane + st < 64 && okey == key) len += olen;
+  }
+  const int prev = __shfl_up(key, 1);
+  if (key >= 0 && (lane == 0 || prev != key)) atomicAdd(&b.a0[key], len);
+}
+
+// W: a shift-vector component as a word of the dtype's size (copied, never computed with)
+template <typename W>
+__device__ __forceinline__ void gb_emit(const BuildDev& b, const BuildOut& o, int64_t q, int64_t e, int c, int j) {
+  o.center[q] = c;
+  o.nbr[q] = j;
+  if (o.perm) o.perm[q] = int32_t(e);
+  if (o.shift_vec) {
+    W* dst = static_cast<W*>(o.shift_vec) + 3 * q;
+    if (b.shift_vec) {
+      const W* sv = static_cast<const W*>(b.shift_vec) + 3 * e;
+      dst[0] = sv[0];
+      dst[1] = sv[1];
+      dst[2] = sv[2];
+    } else {
+      dst[0] = dst[1] = dst[2] = W(0);
+    }
+  }
+  if (o.transposed) atomicAdd(&b.a1[j], 1);
+}
+
+template <typename IT, typename W, bool TYPED>
+__global__ __launch_bounds__(256) void gb_place_kernel(BuildDev b, const int32_t* rowptr, BuildOut o) {
+  const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (e >= b.E || (b.res[kResBadCenter] | b.res[kResBadNbr])) return;
+  if constexpr (TYPED) {
+    if (!b.keepf[e]) return;
+  }
+  const IT* r0 = static_cast<const IT*>(b.rows);
+  const int c = int(r0[e]);
+  if (b.res[kResUnsorted]) {  // a slot of the segment, in arrival order: gb_sort_kernel ranks the segment afterwards
+    b.permw[rowptr[c] + atomicAdd(&b.a0[c], 1)] = int(e);
+    return;
+  }
+  int64_t q = e;
+  if constexpr (TYPED) q = b.kpos[e];
+  gb_emit<W>(b, o, q, e, c, int(r0[b.stride + e]));
+}
+
+__global__ __launch_bounds__(256) void gb_sort_kernel(BuildDev b, const int32_t* rowptr) {
+  const int64_t a = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (a >= b.N || !b.res[kResUnsorted] || (b.res[kResBadCenter] | b.res[kResBadNbr])) return;  // (wave-uniform)
+  gt_sort_group(threadIdx.x & 63, a, rowptr, b.permw);
+}
+
+template <typename IT, typename W>
+__global__ __launch_bounds__(256) void gb_gather_kernel(BuildDev b, const int32_t* rowptr, BuildOut o) {
+  const int64_t q = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (!b.res[kResUnsorted] || (b.res[kResBadCenter] | b.res[kResBadNbr]) || q >= rowptr[b.N]) return;
+  const IT* r0 = static_cast<const IT*>(b.rows);
+  const int64_t e = b.permw[q];
+  gb_emit<W>(b, o, q, e, int(r0[e]), int(r0[b.stride + e]));
+}
+
+// gt_place_kernel for a list whose length the host does not know (rowptr[N], on the device)
+__global__ __launch_bounds__(256) void gb_tplace_kernel(BuildDev b, const int32_t* rowptr, const int32_t* nbr, const int32_t* t_rowptr,
+                                                        int32_t* t_perm) {
+  const int64_t q = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if ((b.res[kResBadCenter] | b.res[kResBadNbr]) || q >= rowptr[b.N]) return;
+  const int j = nbr[q];
+  t_perm[t_rowptr[j] + atomicAdd(&b.a2[j], 1)] = int32_t(q);
+}
+
+size_t build_scan_ints(size_t N, size_t E) { return std::max(N, E) / kScanBlock + 2; }
+
+int plan_build(const aa_edge_list* in, const aa_nl_types* types, void* ws, size_t ws_bytes, const char* who, BuildDev& b) {
+  const std::string w(who);
+  AA_REQUIRE(in, w + ": null argument");
+  AA_REQUIRE(in->num_atoms >= 0 && in->num_atoms < (int64_t(1) << 31) && in->num_edges >= 0 && in->num_edges < (int64_t(1) << 31),
+             w + ": size out of range (num_atoms and num_edges must lie in [0, 2^31))");
+  AA_REQUIRE(ws, w + ": null workspace");
+  AA_REQUIRE(in->index_is_int64 == 0 || in->index_is_int64 == 1, w + ": index_is_int64 must be 0 or 1");
+  AA_REQUIRE(in->edge_index || in->num_edges == 0, w + ": null edge_index");
+  AA_REQUIRE(in->row_stride >= in->num_edges, w + ": row_stride smaller than num_edges (the rows would overlap)");
+  if (types || in->shift_vec) AA_REQUIRE(in->dtype == AA_F32 || in->dtype == AA_F64, w + ": bad dtype");
+  AA_REQUIRE(!types || in->pos || in->num_atoms == 0, w + ": per-type-pair cutoffs need positions (null pos)");
+  if (ws_bytes < aa_graph_build_workspace_bytes(in->num_atoms, in->num_edges)) return fail(AA_ERR_WORKSPACE, w + ": workspace too small");
+  const size_t N = size_t(in->num_atoms), E = size_t(in->num_edges);
+  char* base = static_cast<char*>(ws);
+  auto take = [&](size_t bytes) {
+    char* r = base;
+    base += align_up(bytes);
+    return r;
+  };
+  b.N = in->num_atoms;
+  b.E = in->num_edges;
+  b.stride = in->row_stride;
+  b.rows = in->edge_index;
+  b.shift_vec = in->shift_vec;
+  b.a0 = reinterpret_cast<int*>(take(sizeof(int) * (N + 1)));
+  b.a1 = reinterpret_cast<int*>(take(sizeof(int) * (N + 1)));
+  b.a2 = reinterpret_cast<int*>(take(sizeof(int) * (N + 1)));
+  b.scan_tmp = reinterpret_cast<int*>(take(sizeof(int) * build_scan_ints(N, E)));
+  b.p.rc2 = reinterpret_cast<const double*>(take(kTableBytes));
+  b.res = reinterpret_cast<int*>(take(sizeof(int) * kResInts));
+  b.permw = reinterpret_cast<int*>(take(sizeof(int) * E));
+  b.keepf = reinterpret_cast<int*>(take(sizeof(int) * E));
+  b.kpos = reinterpret_cast<int*>(take(sizeof(int) * (E + 1)));
+  b.p.N = b.N;
+  b.p.E = b.E;
+  b.p.pos = in->pos;
+  b.p.shift_vec = in->shift_vec;
+  b.p.bad_type = b.res + kResBadType;
+  if (types) {
+    b.p.atom_types = types->atom_types;
+    b.p.T = types->num_types;
+  }
+  return AA_OK;
+}
+
+template <typename IT>
+void launch_build_count(const BuildDev& b, const aa_nl_types* types, int dtype, dim3 grid, hipStream_t s) {
+  if (!types) {
+    hipLaunchKernelGGL((gb_count_kernel<IT, float, int32_t, false>), grid, dim3(256), 0, s, b);
+  } else if (dtype == AA_F32) {
+    if (types->types_are_int64)
+      hipLaunchKernelGGL((gb_count_kernel<IT, float, int64_t, true>), grid, dim3(256), 0, s, b);
+    else
+      hipLaunchKernelGGL((gb_count_kernel<IT, float, int32_t, true>), grid, dim3(256), 0, s, b);
+  } else {
+    if (types->types_are_int64)
+      hipLaunchKernelGGL((gb_count_kernel<IT, double, int64_t, true>), grid, dim3(256), 0, s, b);
+    else
+      hipLaunchKernelGGL((gb_count_kernel<IT, double, int32_t, true>), grid, dim3(256), 0, s, b);
+  }
+}
+
+template <typename IT, typename W>
+void launch_build_fill(const BuildDev& b, bool typed, const int32_t* rowptr, const BuildOut& o, dim3 grid, hipStream_t s) {
+  if (typed)
+    hipLaunchKernelGGL((gb_place_kernel<IT, W, true>), grid, dim3(256), 0, s, b, rowptr, o);
+  else
+    hipLaunchKernelGGL((gb_place_kernel<IT, W, false>), grid, dim3(256), 0, s, b, rowptr, o);
+  hipLaunchKernelGGL(gb_sort_kernel, dim3((unsigned)((b.N + 3) / 4)), dim3(256), 0, s, b, rowptr);
+  hipLaunchKernelGGL((gb_gather_kernel<IT, W>), grid, dim3(256), 0, s, b, rowptr, o);
+}
+
+}  // namespace
+
+extern "C" size_t aa_graph_build_workspace_bytes(int64_t num_atoms, int64_t num_edges) {
+  const size_t N = size_t(std::max<int64_t>(0, num_atoms)), E = size_t(std::max<int64_t>(0, num_edges));
+  return 3 * align_up(sizeof(int) * (N + 1)) + align_up(sizeof(int) * build_scan_ints(N, E)) + align_up(kTableBytes) +
+         align_up(sizeof(int) * kResInts) + 2 * align_up(sizeof(int) * E) + align_up(sizeof(int) * (E + 1));
+}
+
+extern "C" int aa_graph_build_count(const aa_edge_list* in, const aa_nl_types* types, void* workspace, size_t workspace_bytes,
+                                    int32_t* out_rowptr, int64_t* out_num_edges, int32_t hints3_host[3], int32_t* input_is_sorted,
+                                    aa_stream stream) {
+  const char* who = "aa_graph_build_count";
+  BuildDev b{};
+  std::vector<double> rc2;
+  if (types) {  // (before the workspace check, like aa_graph_prune_count)
+    double r_max = 0.0;
+    if (int rc = check_types(types, in ? in->num_atoms : 0, 0.0, who, rc2, r_max)) return rc;
+  }
+  if (int rc = plan_build(in, types, workspace, workspace_bytes, who, b)) return rc;
+  AA_REQUIRE(out_rowptr && out_num_edges, std::string(who) + ": null output");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  AA_CHECK_HIP(hipMemsetAsync(b.a0, 0, sizeof(int) * (size_t(b.N) + 1), s));
+  AA_CHECK_HIP(hipMemsetAsync(b.res, 0, sizeof(int) * kResInts, s));
+  if (types) AA_CHECK_HIP(hipMemcpyAsync(const_cast<double*>(b.p.rc2), rc2.data(), sizeof(double) * rc2.size(), hipMemcpyHostToDevice, s));
+  if (b.E > 0) {
+    const dim3 grid((unsigned)((b.E + 255) / 256));
+    if (in->index_is_int64)
+      launch_build_count<int64_t>(b, types, in->dtype, grid, s);
+    else
+      launch_build_count<int32_t>(b, types, in->dtype, grid, s);
+  }
+  launch_scan(b.a0, out_rowptr, b.N, b.scan_tmp, s);
+  hipLaunchKernelGGL(gt_hints_kernel, dim3(1), dim3(256), 3 * 256 * sizeof(int), s, b.N, out_rowptr, b.res + kResHints);
+  if (types && b.E > 0) launch_scan(b.keepf, b.kpos, b.E, b.scan_tmp, s);
+  AA_CHECK_HIP(hipGetLastError());
+  int32_t total = 0, res[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  AA_CHECK_HIP(hipMemcpyAsync(&total, out_rowptr + b.N, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  AA_CHECK_HIP(hipMemcpyAsync(res, b.res, sizeof(res), hipMemcpyDeviceToHost, s));
+  AA_CHECK_HIP(hipStreamSynchronize(s));
+  AA_REQUIRE(!res[kResBadCenter], std::string(who) + ": edge_index row 0 (centers) holds an index outside [0, num_atoms) at edge " +
+                                      std::to_string(res[kResBadCenter] - 1));
+  AA_REQUIRE(!res[kResBadNbr], std::string(who) + ": edge_index row 1 (neighbours) holds an index outside [0, num_atoms) at edge " +
+                                   std::to_string(res[kResBadNbr] - 1));
+  AA_REQUIRE(!res[kResBadType], std::string(who) + ": atom_types outside [0, num_types)");
+  *out_num_edges = total;
+  if (hints3_host)
+    for (int q = 0; q < 3; ++q) hints3_host[q] = res[kResHints + q];
+  if (input_is_sorted) *input_is_sorted = res[kResUnsorted] ? 0 : 1;
+  return AA_OK;
+}
+
+extern "C" int aa_graph_build_fill(const aa_edge_list* in, const aa_nl_types* types, void* workspace, size_t workspace_bytes,
+                                   const int32_t* out_rowptr, int32_t* center, int32_t* nbr, int32_t* perm, void* out_shift_vec,
+                                   int32_t* t_rowptr, int32_t* t_perm, aa_stream stream) {
+  const char* who = "aa_graph_build_fill";
+  BuildDev b{};
+  AA_REQUIRE(!types || (types->num_types >= 1 && types->num_types <= kMaxTypes), std::string(who) + ": num_types must lie in [1, 64]");
+  if (int rc = plan_build(in, types, workspace, workspace_bytes, who, b)) return rc;
+  AA_REQUIRE(out_rowptr, std::string(who) + ": null row pointers");
+  AA_REQUIRE((center && nbr) || b.E == 0, std::string(who) + ": null output");
+  AA_REQUIRE((t_rowptr == nullptr) == (t_perm == nullptr) || (t_rowptr && b.E == 0), std::string(who) + ": t_rowptr and t_perm go together");
+  AA_REQUIRE(!out_shift_vec || in->dtype == AA_F32 || in->dtype == AA_F64, std::string(who) + ": bad dtype");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // (flags, keep flags and their prefix sums are where the count call left them; the histogram array becomes the cursor)
+  AA_CHECK_HIP(hipMemsetAsync(b.a0, 0, 3 * align_up(sizeof(int) * (size_t(b.N) + 1)), s));
+  if (perm) b.permw = perm;
+  BuildOut o{center, nbr, perm, out_shift_vec, t_rowptr ? 1 : 0};
+  const dim3 grid((unsigned)((b.E + 255) / 256));
+  if (b.E > 0 && b.N > 0) {  // (edges without atoms: all out of range, the count call has refused them)
+    const bool w64 = in->dtype == AA_F64;
+    if (in->index_is_int64) {
+      if (w64)
+        launch_build_fill<int64_t, uint64_t>(b, types != nullptr, out_rowptr, o, grid, s);
+      else
+        launch_build_fill<int64_t, uint32_t>(b, types != nullptr, out_rowptr, o, grid, s);
+    } else {
+      if (w64)
+        launch_build_fill<int32_t, uint64_t>(b, types != nullptr, out_rowptr, o, grid, s);
+      else
+        launch_build_fill<int32_t, uint32_t>(b, types != nullptr, out_rowptr, o, grid, s);
+    }
+  }
+  if (t_rowptr) {
+    launch_scan(b.a1, t_rowptr, b.N, b.scan_tmp, s);
+    if (b.E > 0 && b.N > 0) {
+      hipLaunchKernelGGL(gb_tplace_kernel, grid, dim3(256), 0, s, b, out_rowptr, nbr, t_rowptr, t_perm);
+      hipLaunchKernelGGL(gt_sort_kernel, dim3((unsigned)((b.N + 3) / 4)), dim3(256), 0, s, b.N, t_rowptr, t_perm);
+    }
+  }
   AA_CHECK_HIP(hipGetLastError());
   return AA_OK;
 }

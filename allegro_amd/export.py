@@ -90,7 +90,7 @@ class ExportableAllegro(torch.nn.Module):
     (nequip ForceStressOutput convention, which is also LAMMPS' sign); in the ghost-atom layout it is the sum over
     the edges handed in, i.e. the local atoms' share, like every other output."""
 
-    def __init__(self, model, device):
+    def __init__(self, model, device, prune: bool = False):
         super().__init__()
         _refuse_pair_potential(model)
         load_native_ops()
@@ -111,9 +111,16 @@ class ExportableAllegro(torch.nn.Module):
             lib.model_plan_destroy(plan)
         self.config = serialize_config(model, layout)  # int list (a constant of the exported program)
         self.register_buffer("weights", blob)
+        # prune: the op reduces the caller's list to the model's per-type-pair cutoffs on the device, from every call's positions
+        # (`allegro_amd_native::energy_forces_pruned`); the table travels as a float list, a constant of the exported program
+        self.cutoffs = [float(v) for v in model.cutoff_table().flatten().tolist()] if prune else None
 
     def forward(self, pos: torch.Tensor, edge_index: torch.Tensor, atom_types: torch.Tensor,
                 shift_vec: Optional[torch.Tensor] = None):
+        if self.cutoffs is not None:
+            e_atom, forces, virial = torch.ops.allegro_amd_native.energy_forces_pruned(pos, edge_index, atom_types, shift_vec,
+                                                                                       self.config, self.weights, self.cutoffs)
+            return e_atom.unsqueeze(-1), e_atom.sum().reshape(1, 1), forces, virial
         e_atom, forces, virial = torch.ops.allegro_amd_native.energy_forces(pos, edge_index, atom_types, shift_vec,
                                                                             self.config, self.weights)
         return e_atom.unsqueeze(-1), e_atom.sum().reshape(1, 1), forces, virial

@@ -477,6 +477,74 @@ class PreparedGraph:
             self.t_rowptr = torch.zeros(num_atoms + 1, dtype=torch.int32, device=edge_index.device)
             self.t_rowptr[1:] = torch.cumsum(torch.bincount(edge_index[1], minlength=num_atoms), 0).to(torch.int32)
 
+    @classmethod
+    def from_edge_index(cls, edge_index: torch.Tensor, atom_types: torch.Tensor, num_atoms: int,
+                        shift_vec: Optional[torch.Tensor] = None, pos: Optional[torch.Tensor] = None, cutoffs=None,
+                        lib: Optional[_lib.AllegroLib] = None) -> "PreparedGraph":
+        """The graph of ANY edge list -- int64 or int32 `edge_index` [2, E], edges in any order, rows a stride apart -- built by the
+        library in one operation (`aa_graph_build_count` / `aa_graph_build_fill`): center-sorted in stable order, transposed CSR
+        and hints included, with ONE host read (the new edge count, the hints, the sortedness of the input).  With `cutoffs`
+        ([T, T], e.g. `model.cutoff_table()`; needs `pos`) only the edges with |r_e| < cutoffs[type_center, type_neighbour] are
+        kept, the predicate of `DeviceNeighborList.prune`.  The fields mean what they mean after `PreparedGraph(...)`; `perm`
+        (int64, the input id of every output edge) is None exactly when the output is the input list unchanged, and
+        `input_is_sorted` tells whether the input's center row was non-decreasing.  An index outside [0, num_atoms) is an
+        AllegroError naming the row and an edge."""
+        if cutoffs is not None and pos is None:
+            raise ValueError("from_edge_index: cutoffs need pos (the per-type-pair predicate is evaluated on the edge vectors)")
+        if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"from_edge_index: edge_index must be an int32 / int64 [2, E] tensor, not {list(edge_index.shape)} {edge_index.dtype}")
+        if lib is None:
+            lib = _lib.load()
+        _require_gpu(lib, edge_index, "PreparedGraph.from_edge_index")
+        N, E, dev = int(num_atoms), int(edge_index.shape[1]), edge_index.device
+        if E > 0 and (edge_index.stride(1) != 1 or edge_index.stride(0) < E):  # (rows a stride apart are read in place)
+            edge_index = edge_index.contiguous()
+        dtype = pos.dtype if pos is not None else (shift_vec.dtype if shift_vec is not None else torch.float32)
+        if dtype not in _TORCH2AA:
+            raise ValueError(f"from_edge_index: pos / shift_vec must be float32 or float64, not {dtype}")
+        if shift_vec is not None and (tuple(shift_vec.shape) != (E, 3) or shift_vec.dtype != dtype or shift_vec.device != dev):
+            raise ValueError(f"from_edge_index: shift_vec must be [{E}, 3] {dtype} on {dev}, not {list(shift_vec.shape)} "
+                             f"{shift_vec.dtype} on {shift_vec.device}")
+        if pos is not None and (tuple(pos.shape) != (N, 3) or pos.device != dev):
+            raise ValueError(f"from_edge_index: pos must be [{N}, 3] on {dev}, not {list(pos.shape)} on {pos.device}")
+        sv = None if shift_vec is None else shift_vec.detach().contiguous()
+        p = None if pos is None else pos.detach().contiguous()
+        types, keep = (None, None) if cutoffs is None else _nl_types(atom_types, cutoffs, N, dev, "from_edge_index")
+        tref = None if types is None else C.byref(types)
+        inp = _lib.EdgeList(N, E, edge_index.data_ptr() if E else None, edge_index.stride(0) if E else 0,
+                            int(edge_index.dtype == torch.int64), _TORCH2AA[dtype], p.data_ptr() if p is not None and N else None,
+                            sv.data_ptr() if sv is not None and E else None)
+        g = cls.__new__(cls)
+        nbytes = lib.lib.aa_graph_build_workspace_bytes(N, E)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        g.rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
+        n_edges, hints, was_sorted = C.c_int64(), (C.c_int32 * 3)(), C.c_int32()
+        stream = _stream_ptr(edge_index)
+        with _device_ctx(dev):
+            lib.check(lib.lib.aa_graph_build_count(C.byref(inp), tref, ws.data_ptr(), nbytes, g.rowptr.data_ptr(), C.byref(n_edges), hints,
+                                                   C.byref(was_sorted), stream), "aa_graph_build_count")
+            E2 = int(n_edges.value)
+            out = torch.empty((2, E2), dtype=torch.int32, device=dev)
+            perm = torch.empty(E2, dtype=torch.int32, device=dev)
+            g.shift_vec = None if sv is None else torch.empty((E2, 3), dtype=dtype, device=dev)
+            g.t_perm = torch.empty(E2, dtype=torch.int32, device=dev)
+            if E2 > 0:
+                g.t_rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
+                lib.check(lib.lib.aa_graph_build_fill(C.byref(inp), tref, ws.data_ptr(), nbytes, g.rowptr.data_ptr(), out[0].data_ptr(),
+                                                      out[1].data_ptr(), perm.data_ptr(),
+                                                      g.shift_vec.data_ptr() if g.shift_vec is not None else None,
+                                                      g.t_rowptr.data_ptr(), g.t_perm.data_ptr(), stream), "aa_graph_build_fill")
+            else:
+                g.t_rowptr = torch.zeros(N + 1, dtype=torch.int32, device=dev)
+        del keep
+        g.num_atoms, g.num_edges = N, E2
+        g.center, g.nbr = out[0], out[1]
+        g.types = atom_types.reshape(-1).to(torch.int32).contiguous()
+        g.input_is_sorted = bool(was_sorted.value)
+        g.perm = None if g.input_is_sorted and E2 == E else perm.long()
+        g.atom_begin, g.atom_end, g.max_degree = (int(v) for v in hints)
+        return g
+
     def rowptr_host(self):
         """The row pointers as a host int64 array: ONE device read per graph, kept."""
         rp = getattr(self, "_rowptr_host", None)
@@ -1126,8 +1194,16 @@ class HipAllegroModel(torch.nn.Module):
         return neighbor_list(pos, cell, pbc, self.hparams["r_max"], lib=self._bound_lib, atom_types=atom_types,
                              cutoffs=self.cutoff_table())
 
-    def prepare_graph(self, edge_index, atom_types, num_atoms, shift_vec=None) -> PreparedGraph:
-        return PreparedGraph(edge_index, atom_types, num_atoms, shift_vec, lib=self._bound_lib)
+    def prepare_graph(self, edge_index, atom_types, num_atoms, shift_vec=None, pos=None, prune=False) -> PreparedGraph:
+        """`PreparedGraph(...)` of a foreign list.  With `pos` (or `prune`, which needs it) the list goes through
+        `PreparedGraph.from_edge_index` instead -- one library operation, one host read -- and with `prune` it is reduced to the
+        model's own `cutoff_table()` on the way: the edges the envelope turns into exact zeros are never evaluated."""
+        if pos is None and not prune:
+            return PreparedGraph(edge_index, atom_types, num_atoms, shift_vec, lib=self._bound_lib)
+        if pos is None:
+            raise ValueError("prepare_graph: prune=True needs pos")
+        return PreparedGraph.from_edge_index(edge_index, atom_types, num_atoms, shift_vec, pos=pos,
+                                             cutoffs=self.cutoff_table() if prune else None, lib=self._bound_lib)
 
     def energy_forces(self, pos: torch.Tensor, graph: PreparedGraph, with_forces: bool = True, max_block_edges: Optional[int] = None):
         """One pass of the hot path: returns (atom_energy [N], forces [N,3] | None).

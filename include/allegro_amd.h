@@ -549,6 +549,47 @@ int aa_graph_prune_fill(const aa_prune_input* in, const aa_nl_types* types, void
                         const int32_t* out_rowptr, int32_t* out_center, int32_t* out_nbr, void* out_shift_vec, int32_t* kept,
                         aa_stream stream);
 
+/* The aa_graph of the list a host actually has: edge_index [2,E] as the pair_allegro contract hands it over (allegro/_compile.py:
+ * 10-14: int64, centers in row 0, neighbours in row 1, edges in ANY order; int32 rows are taken too), optionally with per-edge shift
+ * vectors, optionally reduced to per-type-pair cutoffs on the way.  One operation instead of a host-side sort + aa_graph_prune_* +
+ * aa_graph_transpose.  Two phases like aa_nl_*, same arguments and the same `workspace` (aa_graph_build_workspace_bytes(num_atoms,
+ * num_edges) bytes of device scratch) for both:
+ *   aa_graph_build_count  writes out_rowptr [N+1] (device), synchronises the stream ONCE and returns E', the three hints
+ *                         {atom_begin, atom_end, max_degree} of the output list (the definition of aa_graph_transpose's hints3; host
+ *                         memory, may be NULL) and whether the input center row was already non-decreasing (may be NULL);
+ *   aa_graph_build_fill   writes center / nbr [E'] and, where not NULL, perm [E'], out_shift_vec [E',3] (`dtype`; zeros when the input
+ *                         has no shifts) and t_rowptr [N+1] / t_perm [E'] (both or neither).  No host read.  (With E' == 0 a caller skips the
+ *                         call and zeroes t_rowptr itself: the call cannot know E' and insists on its pointers.)
+ * Kept edges: all of them with types == NULL; with `types` edge e iff |pos[nbr_e] - pos[center_e] + shift_vec_e|^2 <
+ * cutoffs[type_center][type_nbr]^2 in double -- the predicate of aa_graph_prune_*, the same device function; the checks on `types` and
+ * the clamping of atom types with a device flag are those of aa_graph_prune_count.  `pos` is read only then.
+ * Order: segment a of the output holds the kept edges with center a in ascending input edge id (the stable argsort of the center row,
+ * restricted to the kept edges); perm[q] = input id of output edge q; out_shift_vec[q] = shift_vec[perm[q]].  t_rowptr / t_perm are
+ * what aa_graph_transpose yields for the output list.  All integer, bit-reproducible, independent of the order atomics are served in:
+ * atomics only count; final positions are prefix sums (sorted input) or ranks inside a segment (unsorted input).
+ * Equivalences: types == NULL and a sorted input give the int32 copies of the input rows and perm = identity; a table beyond every
+ * edge length gives the types == NULL output.
+ * Errors: a center or neighbour outside [0, N) is AA_ERR_INVALID from the count call, naming the row and one offending edge id (a
+ * device flag; nothing is read or written out of bounds, and a fill call issued regardless writes no output); E or N >= 2^31, a
+ * row_stride below E: AA_ERR_INVALID; E == 0 and N == 0 are valid (zero row pointers, zero hints).  Outputs must not alias inputs.
+ * (No deviation from the proposed signatures.) */
+typedef struct {
+  int64_t num_atoms, num_edges;
+  const void* edge_index;  /* device; row 0 = centers at [0,E), row 1 = neighbours at edge_index + row_stride (elements) */
+  int64_t row_stride;
+  int32_t index_is_int64;  /* 1: int64 (the pair_allegro contract), 0: int32                          */
+  int32_t dtype;           /* aa_dtype of pos / shift_vec                                             */
+  const void* pos;         /* [N,3] device; read only when `types` is given                           */
+  const void* shift_vec;   /* [E,3] device in input edge order, or NULL                               */
+} aa_edge_list;
+size_t aa_graph_build_workspace_bytes(int64_t num_atoms, int64_t num_edges);
+int aa_graph_build_count(const aa_edge_list* in, const aa_nl_types* types /* NULL: keep every edge */, void* workspace,
+                         size_t workspace_bytes, int32_t* out_rowptr, int64_t* out_num_edges, int32_t hints3_host[3],
+                         int32_t* input_is_sorted, aa_stream stream);
+int aa_graph_build_fill(const aa_edge_list* in, const aa_nl_types* types, void* workspace, size_t workspace_bytes,
+                        const int32_t* out_rowptr, int32_t* center, int32_t* nbr, int32_t* perm, void* out_shift_vec,
+                        int32_t* t_rowptr, int32_t* t_perm, aa_stream stream);
+
 /* Transposed CSR of a center-sorted edge list on the device -- `t_rowptr` [N+1], `t_perm` [E]: edge ids grouped by NEIGHBOUR atom in
  * ascending order (= the stable argsort of `nbr`), what aa_graph.t_rowptr / t_perm ask for so that forces are gathered per atom in a
  * fixed order -- and, with `hints3` != NULL (device int32[3]; needs `rowptr`), the three graph hints {atom_begin, atom_end,
