@@ -249,24 +249,18 @@ class AllegroLib:
         L.aa_model_plan_describe.restype = C.c_int
         L.aa_model_check.argtypes = [C.c_void_p, C.c_void_p]
         L.aa_model_check.restype = C.c_int
-        L.aa_model_virial.argtypes = [C.c_void_p, C.POINTER(Graph), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-        L.aa_model_virial.restype = C.c_int
-        L.aa_model_atom_virial.argtypes = [C.c_void_p, C.POINTER(Graph), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
-        L.aa_model_atom_virial.restype = C.c_int
-        L.aa_model_heat_flux.argtypes = [C.c_void_p, C.POINTER(Graph), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.aa_model_heat_flux.restype = C.c_int
+        # the observables of a finished force step and their blocked twins (max_block_edges behind the graph): name -> what lies
+        # between the workspace and (out, stream)
+        for name, mid in (("virial", []), ("atom_virial", [C.c_int]), ("heat_flux", [C.c_void_p])):
+            for fn, cap in ((f"aa_model_{name}", []), (f"aa_model_blocked_{name}", [C.c_int64])):
+                getattr(L, fn).argtypes = [C.c_void_p, C.POINTER(Graph)] + cap + [C.c_void_p, C.c_size_t] + mid + [C.c_void_p, C.c_void_p]
+                getattr(L, fn).restype = C.c_int
         _i64p = C.POINTER(C.c_int64)
         L.aa_model_blocked_workspace_bytes.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int]
         L.aa_model_blocked_workspace_bytes.restype = C.c_size_t
         L.aa_model_energy_forces_blocked.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Graph), C.c_void_p, C.c_int32, _i64p, _i64p, C.c_void_p,
                                                      C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.aa_model_energy_forces_blocked.restype = C.c_int
-        L.aa_model_blocked_virial.argtypes = [C.c_void_p, C.POINTER(Graph), C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-        L.aa_model_blocked_virial.restype = C.c_int
-        L.aa_model_blocked_atom_virial.argtypes = [C.c_void_p, C.POINTER(Graph), C.c_int64, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
-        L.aa_model_blocked_atom_virial.restype = C.c_int
-        L.aa_model_blocked_heat_flux.argtypes = [C.c_void_p, C.POINTER(Graph), C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.aa_model_blocked_heat_flux.restype = C.c_int
         L.aa_nl_workspace_bytes.argtypes = [C.c_int64]
         L.aa_nl_workspace_bytes.restype = C.c_size_t
         L.aa_nl_count.argtypes = [C.POINTER(NlInput), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]

@@ -725,6 +725,30 @@ int launch_edge_backward(const EdgeBwdArgs& b, hipStream_t stream) {
   return AA_OK;
 }
 
+// Fixed-order sum of K doubles per lane over the edges: the 256 lanes of a block through LDS (block_tree_sum), then one block over
+// the block partials in block order, rounded once (edge_sum_final_kernel).  No atomics: the same bits on every call.
+template <int K>
+__device__ inline void block_tree_sum(double* sP /* [256][K] */, const double (&w)[K], double* partial /* [gridDim.x][K] */) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) sP[threadIdx.x * K + k] = w[k];
+  __syncthreads();
+  for (int st = 128; st >= 1; st >>= 1) {
+    if (int(threadIdx.x) < st)
+      for (int k = 0; k < K; ++k) sP[threadIdx.x * K + k] += sP[(threadIdx.x + st) * K + k];
+    __syncthreads();
+  }
+  if (threadIdx.x < K) partial[blockIdx.x * K + threadIdx.x] = sP[threadIdx.x];
+}
+template <typename T, int K, bool NEGATE>
+__global__ __launch_bounds__(64) void edge_sum_final_kernel(const double* partial, int nblocks, void* out) {
+  if (threadIdx.x < K) {
+    double s = 0.0;
+    for (int b2 = 0; b2 < nblocks; ++b2) s += partial[b2 * K + threadIdx.x];
+    static_cast<T*>(out)[threadIdx.x] = NEGATE ? T(0.0 - s) : T(s);  // (0.0 - s: an empty list gives +0)
+  }
+}
+static int edge_sum_blocks(int64_t E) { return int(std::min<int64_t>(kVirialBlocks, std::max<int64_t>(1, (E + 255) / 256))); }
+
 // strain derivative: per-block partial sums in double (fixed order), then one block adds the partials
 template <typename T>
 __global__ __launch_bounds__(256) void virial_partial_kernel(VirialArgs a) {
@@ -742,29 +766,13 @@ __global__ __launch_bounds__(256) void virial_partial_kernel(VirialArgs a) {
     w[3] += dy * rx; w[4] += dy * ry; w[5] += dy * rz;
     w[6] += dz * rx; w[7] += dz * ry; w[8] += dz * rz;
   }
-#pragma unroll
-  for (int k = 0; k < 9; ++k) sP[threadIdx.x * 9 + k] = w[k];
-  __syncthreads();
-  for (int st = 128; st >= 1; st >>= 1) {
-    if (int(threadIdx.x) < st)
-      for (int k = 0; k < 9; ++k) sP[threadIdx.x * 9 + k] += sP[(threadIdx.x + st) * 9 + k];
-    __syncthreads();
-  }
-  if (threadIdx.x < 9) a.partial[blockIdx.x * 9 + threadIdx.x] = sP[threadIdx.x];
-}
-template <typename T>
-__global__ __launch_bounds__(64) void virial_final_kernel(VirialArgs a, int nblocks) {
-  if (threadIdx.x < 9) {
-    double s = 0.0;
-    for (int b2 = 0; b2 < nblocks; ++b2) s += a.partial[b2 * 9 + threadIdx.x];
-    static_cast<T*>(a.out)[threadIdx.x] = T(s);
-  }
+  block_tree_sum<9>(sP, w, a.partial);
 }
 template <typename T>
 int launch_virial(const VirialArgs& a, hipStream_t stream) {
-  const int nb = int(std::min<int64_t>(kVirialBlocks, std::max<int64_t>(1, (a.E + 255) / 256)));
+  const int nb = edge_sum_blocks(a.E);
   hipLaunchKernelGGL(virial_partial_kernel<T>, dim3(nb), dim3(256), sizeof(double) * 256 * 9, stream, a);
-  hipLaunchKernelGGL(virial_final_kernel<T>, dim3(1), dim3(64), 0, stream, a, nb);
+  hipLaunchKernelGGL((edge_sum_final_kernel<T, 9, false>), dim3(1), dim3(64), 0, stream, a.partial, nb, a.out);
   AA_CHECK_HIP(hipGetLastError());
   return AA_OK;
 }
@@ -789,30 +797,14 @@ __global__ __launch_bounds__(256) void heat_flux_partial_kernel(HeatFluxArgs a) 
     jy += double(v[1]) * r * p;
     jz += double(v[2]) * r * p;
   }
-  sP[threadIdx.x * 3] = jx;
-  sP[threadIdx.x * 3 + 1] = jy;
-  sP[threadIdx.x * 3 + 2] = jz;
-  __syncthreads();
-  for (int st = 128; st >= 1; st >>= 1) {
-    if (int(threadIdx.x) < st)
-      for (int k = 0; k < 3; ++k) sP[threadIdx.x * 3 + k] += sP[(threadIdx.x + st) * 3 + k];
-    __syncthreads();
-  }
-  if (threadIdx.x < 3) a.partial[blockIdx.x * 3 + threadIdx.x] = sP[threadIdx.x];
-}
-template <typename T>
-__global__ __launch_bounds__(64) void heat_flux_final_kernel(HeatFluxArgs a, int nblocks) {
-  if (threadIdx.x < 3) {
-    double s = 0.0;
-    for (int b2 = 0; b2 < nblocks; ++b2) s += a.partial[b2 * 3 + threadIdx.x];
-    static_cast<T*>(a.out)[threadIdx.x] = T(0.0 - s);  // (an empty list gives +0)
-  }
+  const double w[3] = {jx, jy, jz};
+  block_tree_sum<3>(sP, w, a.partial);
 }
 template <typename T>
 int launch_heat_flux(const HeatFluxArgs& a, hipStream_t stream) {
-  const int nb = int(std::min<int64_t>(kVirialBlocks, std::max<int64_t>(1, (a.E + 255) / 256)));
+  const int nb = edge_sum_blocks(a.E);
   hipLaunchKernelGGL(heat_flux_partial_kernel<T>, dim3(nb), dim3(256), sizeof(double) * 256 * 3, stream, a);
-  hipLaunchKernelGGL(heat_flux_final_kernel<T>, dim3(1), dim3(64), 0, stream, a, nb);
+  hipLaunchKernelGGL((edge_sum_final_kernel<T, 3, true>), dim3(1), dim3(64), 0, stream, a.partial, nb, a.out);
   AA_CHECK_HIP(hipGetLastError());
   return AA_OK;
 }

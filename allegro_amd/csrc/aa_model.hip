@@ -3020,63 +3020,6 @@ extern "C" int aa_model_energy_forces_profiled(const aa_model_plan* plan, const 
   return rc;
 }
 
-extern "C" int aa_model_virial(const aa_model_plan* plan, const aa_graph* graph, void* workspace, size_t workspace_bytes,
-                               void* virial9, aa_stream stream) {
-  AA_REQUIRE(plan && graph && workspace && virial9, "aa_model_virial: null argument");
-  const Workspace w = layout_workspace(plan, graph->num_atoms, graph->num_edges, 1);
-  if (w.total > workspace_bytes) return fail(AA_ERR_WORKSPACE, "aa_model_virial: workspace too small (was it sized with forces?)");
-  char* base = static_cast<char*>(workspace);
-  VirialArgs a{graph->num_edges, base + w.dvec, base + w.vec, reinterpret_cast<double*>(base + w.vir_part), virial9};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return plan->cfg.dtype == AA_F32 ? launch_virial<float>(a, s) : launch_virial<double>(a, s);
-}
-
-extern "C" int aa_model_atom_virial(const aa_model_plan* plan, const aa_graph* graph, void* workspace, size_t workspace_bytes,
-                                    int attribution, void* out_n9, aa_stream stream) {
-  AA_REQUIRE(plan && graph && workspace && out_n9, "aa_model_atom_virial: null argument");
-  double cc, cn;
-  switch (attribution) {
-    case AA_ATOM_VIRIAL_CENTER: cc = 1.0, cn = 0.0; break;
-    case AA_ATOM_VIRIAL_NEIGHBOR: cc = 0.0, cn = 1.0; break;
-    case AA_ATOM_VIRIAL_SPLIT: cc = cn = 0.5; break;
-    default: return fail(AA_ERR_INVALID, "aa_model_atom_virial: unknown attribution " + std::to_string(attribution) +
-                                             " (AA_ATOM_VIRIAL_CENTER, _NEIGHBOR or _SPLIT)");
-  }
-  // (no atomics fallback: a per-atom tensor that changes from call to call is what this entry point exists to avoid)
-  // (a list without edges has row pointers and an EMPTY t_perm, which a host may well pass as a null pointer: nothing reads it)
-  if (cn != 0.0 && !(graph->t_rowptr && (graph->t_perm || graph->num_edges == 0)))
-    return fail(AA_ERR_INVALID, "aa_model_atom_virial: the neighbor and split attributions need the transposed CSR "
-                                "(aa_graph.t_rowptr / t_perm, aa_graph_transpose)");
-  const Workspace w = layout_workspace(plan, graph->num_atoms, graph->num_edges, 1);
-  if (w.total > workspace_bytes) return fail(AA_ERR_WORKSPACE, "aa_model_atom_virial: workspace too small (was it sized with forces?)");
-  char* base = static_cast<char*>(workspace);
-  AtomVirialArgs a{graph->num_atoms, graph->rowptr, graph->t_rowptr, graph->t_perm, base + w.dvec, base + w.vec, cc, cn, out_n9};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return plan->cfg.dtype == AA_F32 ? launch_atom_virial<float>(a, s) : launch_atom_virial<double>(a, s);
-}
-
-namespace {
-// shared by aa_model_heat_flux and its blocked twin: the argument checks and the launch pair, on the two [E,4] arrays at `dvec` / `vec`
-int heat_flux_from(const aa_model_plan* plan, const aa_graph* graph, const char* who, char* dvec, char* vec, char* vir_part,
-                   const void* velocities, void* flux3, aa_stream stream) {
-  if (!flux3) return fail(AA_ERR_INVALID, std::string(who) + ": null flux3");
-  if (!velocities && graph->num_atoms > 0) return fail(AA_ERR_INVALID, std::string(who) + ": null velocities");
-  if (graph->num_edges > 0 && !graph->nbr) return fail(AA_ERR_INVALID, std::string(who) + ": null neighbor array (aa_graph.nbr)");
-  HeatFluxArgs a{graph->num_edges, dvec, vec, graph->nbr, velocities, reinterpret_cast<double*>(vir_part), flux3};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return plan->cfg.dtype == AA_F32 ? launch_heat_flux<float>(a, s) : launch_heat_flux<double>(a, s);
-}
-}  // namespace
-
-extern "C" int aa_model_heat_flux(const aa_model_plan* plan, const aa_graph* graph, void* workspace, size_t workspace_bytes,
-                                  const void* velocities, void* flux3, aa_stream stream) {
-  AA_REQUIRE(plan && graph && workspace, "aa_model_heat_flux: null argument");
-  const Workspace w = layout_workspace(plan, graph->num_atoms, graph->num_edges, 1);
-  if (w.total > workspace_bytes) return fail(AA_ERR_WORKSPACE, "aa_model_heat_flux: workspace too small (was it sized with forces?)");
-  char* base = static_cast<char*>(workspace);
-  return heat_flux_from(plan, graph, "aa_model_heat_flux", base + w.dvec, base + w.vec, base + w.vir_part, velocities, flux3, stream);
-}
-
 // ------------------------------------------------------------------------------------------------
 // blocked step: the frame one block of center atoms after the other, in one arena
 // ------------------------------------------------------------------------------------------------
@@ -3169,52 +3112,120 @@ extern "C" int aa_model_energy_forces_blocked(const aa_model_plan* plan, const v
              : run_blocked<double>(plan, dev_weights, graph, pos, num_blocks, block_atoms, block_edges, bw, base, atom_energy, forces, s);
 }
 
+// ------------------------------------------------------------------------------------------------
+// What is read off a finished force step: the virial, the per-atom virial and the potential part of the heat flux, each from the
+// [E,4] rows the step left in its workspace.  Where those rows lie -- the unblocked step's workspace or the blocked step's frame
+// arrays -- is all that differs between an entry point and its blocked twin, and locate_step_rows answers it.
+// ------------------------------------------------------------------------------------------------
+namespace {
+// where a force step left its [E,4] rows and the reduction scratch
+struct StepRows {
+  char *vec, *dvec, *vir_part;
+};
+
+// The rows of the step that ran in `workspace`: the unblocked one (max_block_edges < 0) or the blocked one at this max_block_edges.
+// Refuses, in the name of `who`, a workspace smaller than that step's.
+int locate_step_rows(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges, void* workspace, size_t workspace_bytes,
+                     const char* who, StepRows* out) {
+  char* base = static_cast<char*>(workspace);
+  if (max_block_edges < 0) {
+    const Workspace w = layout_workspace(plan, graph->num_atoms, graph->num_edges, 1);
+    if (w.total > workspace_bytes) return fail(AA_ERR_WORKSPACE, std::string(who) + ": workspace too small (was it sized with forces?)");
+    *out = StepRows{base + w.vec, base + w.dvec, base + w.vir_part};
+    return AA_OK;
+  }
+  const BlockedWorkspace bw = layout_blocked(plan, graph->num_atoms, graph->num_edges, std::min(max_block_edges, graph->num_edges), 1);
+  if (bw.total > workspace_bytes)
+    return fail(AA_ERR_WORKSPACE, std::string(who) + ": workspace too small (was it sized with forces, at this max_block_edges?)");
+  *out = StepRows{base + bw.vec, base + bw.dvec, base + bw.arena.vir_part};
+  return AA_OK;
+}
+
+// Each body serves an entry point and its blocked twin: `who` names the caller in every message, max_block_edges < 0 is the unblocked step.
+
+int virial_from(const aa_model_plan* plan, const aa_graph* graph, const char* who, int64_t max_block_edges, void* workspace,
+                size_t workspace_bytes, void* virial9, aa_stream stream) {
+  StepRows r;
+  if (int rc = locate_step_rows(plan, graph, max_block_edges, workspace, workspace_bytes, who, &r)) return rc;
+  VirialArgs a{graph->num_edges, r.dvec, r.vec, reinterpret_cast<double*>(r.vir_part), virial9};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return plan->cfg.dtype == AA_F32 ? launch_virial<float>(a, s) : launch_virial<double>(a, s);
+}
+
+int atom_virial_from(const aa_model_plan* plan, const aa_graph* graph, const char* who, int64_t max_block_edges, void* workspace,
+                     size_t workspace_bytes, int attribution, void* out_n9, aa_stream stream) {
+  double cc, cn;
+  switch (attribution) {
+    case AA_ATOM_VIRIAL_CENTER: cc = 1.0, cn = 0.0; break;
+    case AA_ATOM_VIRIAL_NEIGHBOR: cc = 0.0, cn = 1.0; break;
+    case AA_ATOM_VIRIAL_SPLIT: cc = cn = 0.5; break;
+    default: return fail(AA_ERR_INVALID, std::string(who) + ": unknown attribution " + std::to_string(attribution) +
+                                             " (AA_ATOM_VIRIAL_CENTER, _NEIGHBOR or _SPLIT)");
+  }
+  // (no atomics fallback: a per-atom tensor that changes from call to call is what this entry point exists to avoid)
+  // (a list without edges has row pointers and an EMPTY t_perm, which a host may well pass as a null pointer: nothing reads it)
+  if (cn != 0.0 && !(graph->t_rowptr && (graph->t_perm || graph->num_edges == 0)))
+    return fail(AA_ERR_INVALID, std::string(who) + ": the neighbor and split attributions need the transposed CSR "
+                                                   "(aa_graph.t_rowptr / t_perm, aa_graph_transpose)");
+  StepRows r;  // (located last: an unknown attribution or a missing transposed CSR is refused whatever the workspace)
+  if (int rc = locate_step_rows(plan, graph, max_block_edges, workspace, workspace_bytes, who, &r)) return rc;
+  AtomVirialArgs a{graph->num_atoms, graph->rowptr, graph->t_rowptr, graph->t_perm, r.dvec, r.vec, cc, cn, out_n9};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return plan->cfg.dtype == AA_F32 ? launch_atom_virial<float>(a, s) : launch_atom_virial<double>(a, s);
+}
+
+int heat_flux_from(const aa_model_plan* plan, const aa_graph* graph, const char* who, int64_t max_block_edges, void* workspace,
+                   size_t workspace_bytes, const void* velocities, void* flux3, aa_stream stream) {
+  StepRows r;
+  if (int rc = locate_step_rows(plan, graph, max_block_edges, workspace, workspace_bytes, who, &r)) return rc;
+  if (!flux3) return fail(AA_ERR_INVALID, std::string(who) + ": null flux3");
+  if (!velocities && graph->num_atoms > 0) return fail(AA_ERR_INVALID, std::string(who) + ": null velocities");
+  if (graph->num_edges > 0 && !graph->nbr) return fail(AA_ERR_INVALID, std::string(who) + ": null neighbor array (aa_graph.nbr)");
+  HeatFluxArgs a{graph->num_edges, r.dvec, r.vec, graph->nbr, velocities, reinterpret_cast<double*>(r.vir_part), flux3};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return plan->cfg.dtype == AA_F32 ? launch_heat_flux<float>(a, s) : launch_heat_flux<double>(a, s);
+}
+}  // namespace
+
+// The entry points: null checks, the blocked ones refuse a negative max_block_edges, then the body.
+
+extern "C" int aa_model_virial(const aa_model_plan* plan, const aa_graph* graph, void* workspace, size_t workspace_bytes,
+                               void* virial9, aa_stream stream) {
+  AA_REQUIRE(plan && graph && workspace && virial9, "aa_model_virial: null argument");
+  return virial_from(plan, graph, "aa_model_virial", -1, workspace, workspace_bytes, virial9, stream);
+}
+
 extern "C" int aa_model_blocked_virial(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges, void* workspace,
                                        size_t workspace_bytes, void* virial9, aa_stream stream) {
   AA_REQUIRE(plan && graph && workspace && virial9, "aa_model_blocked_virial: null argument");
   AA_REQUIRE(max_block_edges >= 0, "aa_model_blocked_virial: negative max_block_edges");
-  const BlockedWorkspace bw = layout_blocked(plan, graph->num_atoms, graph->num_edges, std::min(max_block_edges, graph->num_edges), 1);
-  if (bw.total > workspace_bytes) return fail(AA_ERR_WORKSPACE, "aa_model_blocked_virial: workspace too small (was it sized with forces, at this max_block_edges?)");
-  char* base = static_cast<char*>(workspace);
-  VirialArgs a{graph->num_edges, base + bw.dvec, base + bw.vec, reinterpret_cast<double*>(base + bw.arena.vir_part), virial9};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return plan->cfg.dtype == AA_F32 ? launch_virial<float>(a, s) : launch_virial<double>(a, s);
+  return virial_from(plan, graph, "aa_model_blocked_virial", max_block_edges, workspace, workspace_bytes, virial9, stream);
+}
+
+extern "C" int aa_model_atom_virial(const aa_model_plan* plan, const aa_graph* graph, void* workspace, size_t workspace_bytes,
+                                    int attribution, void* out_n9, aa_stream stream) {
+  AA_REQUIRE(plan && graph && workspace && out_n9, "aa_model_atom_virial: null argument");
+  return atom_virial_from(plan, graph, "aa_model_atom_virial", -1, workspace, workspace_bytes, attribution, out_n9, stream);
 }
 
 extern "C" int aa_model_blocked_atom_virial(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges, void* workspace,
                                             size_t workspace_bytes, int attribution, void* out_n9, aa_stream stream) {
   AA_REQUIRE(plan && graph && workspace && out_n9, "aa_model_blocked_atom_virial: null argument");
   AA_REQUIRE(max_block_edges >= 0, "aa_model_blocked_atom_virial: negative max_block_edges");
-  double cc, cn;
-  switch (attribution) {
-    case AA_ATOM_VIRIAL_CENTER: cc = 1.0, cn = 0.0; break;
-    case AA_ATOM_VIRIAL_NEIGHBOR: cc = 0.0, cn = 1.0; break;
-    case AA_ATOM_VIRIAL_SPLIT: cc = cn = 0.5; break;
-    default: return fail(AA_ERR_INVALID, "aa_model_blocked_atom_virial: unknown attribution " + std::to_string(attribution) +
-                                             " (AA_ATOM_VIRIAL_CENTER, _NEIGHBOR or _SPLIT)");
-  }
-  if (cn != 0.0 && !(graph->t_rowptr && (graph->t_perm || graph->num_edges == 0)))
-    return fail(AA_ERR_INVALID, "aa_model_blocked_atom_virial: the neighbor and split attributions need the transposed CSR "
-                                "(aa_graph.t_rowptr / t_perm, aa_graph_transpose)");
-  const BlockedWorkspace bw = layout_blocked(plan, graph->num_atoms, graph->num_edges, std::min(max_block_edges, graph->num_edges), 1);
-  if (bw.total > workspace_bytes)
-    return fail(AA_ERR_WORKSPACE, "aa_model_blocked_atom_virial: workspace too small (was it sized with forces, at this max_block_edges?)");
-  char* base = static_cast<char*>(workspace);
-  AtomVirialArgs a{graph->num_atoms, graph->rowptr, graph->t_rowptr, graph->t_perm, base + bw.dvec, base + bw.vec, cc, cn, out_n9};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return plan->cfg.dtype == AA_F32 ? launch_atom_virial<float>(a, s) : launch_atom_virial<double>(a, s);
+  return atom_virial_from(plan, graph, "aa_model_blocked_atom_virial", max_block_edges, workspace, workspace_bytes, attribution, out_n9, stream);
+}
+
+extern "C" int aa_model_heat_flux(const aa_model_plan* plan, const aa_graph* graph, void* workspace, size_t workspace_bytes,
+                                  const void* velocities, void* flux3, aa_stream stream) {
+  AA_REQUIRE(plan && graph && workspace, "aa_model_heat_flux: null argument");
+  return heat_flux_from(plan, graph, "aa_model_heat_flux", -1, workspace, workspace_bytes, velocities, flux3, stream);
 }
 
 extern "C" int aa_model_blocked_heat_flux(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges, void* workspace,
                                           size_t workspace_bytes, const void* velocities, void* flux3, aa_stream stream) {
   AA_REQUIRE(plan && graph && workspace, "aa_model_blocked_heat_flux: null argument");
   AA_REQUIRE(max_block_edges >= 0, "aa_model_blocked_heat_flux: negative max_block_edges");
-  const BlockedWorkspace bw = layout_blocked(plan, graph->num_atoms, graph->num_edges, std::min(max_block_edges, graph->num_edges), 1);
-  if (bw.total > workspace_bytes)
-    return fail(AA_ERR_WORKSPACE, "aa_model_blocked_heat_flux: workspace too small (was it sized with forces, at this max_block_edges?)");
-  char* base = static_cast<char*>(workspace);
-  return heat_flux_from(plan, graph, "aa_model_blocked_heat_flux", base + bw.dvec, base + bw.vec, base + bw.arena.vir_part, velocities, flux3,
-                        stream);
+  return heat_flux_from(plan, graph, "aa_model_blocked_heat_flux", max_block_edges, workspace, workspace_bytes, velocities, flux3, stream);
 }
 
 extern "C" int aa_model_debug_tap(const aa_model_plan* plan, const char* name, int64_t N, int64_t E, const void* workspace,

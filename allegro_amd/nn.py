@@ -1239,10 +1239,7 @@ class HipAllegroModel(torch.nn.Module):
             self._ensure_plan()
             self._ensure_weights(pos.device)
             N, E = graph.num_atoms, graph.num_edges
-            need = lib.lib.aa_model_blocked_workspace_bytes(self._plan_handle, N, E, cap, int(with_forces))
-            if self._workspace is None or self._workspace.numel() < need or self._workspace.device != pos.device:
-                self._workspace = None
-                self._workspace = torch.empty(need + need // 16 + (1 << 20), dtype=torch.uint8, device=pos.device)
+            self._ensure_workspace(lib.lib.aa_model_blocked_workspace_bytes(self._plan_handle, N, E, cap, int(with_forces)), pos.device)
             pos = pos.detach().contiguous()
             e_atom = torch.empty(N, dtype=self.dtype, device=pos.device)
             forces = torch.empty((N, 3), dtype=self.dtype, device=pos.device) if with_forces else None
@@ -1276,20 +1273,22 @@ class HipAllegroModel(torch.nn.Module):
                 hi = mid - 1
         return lo
 
+    def _ensure_workspace(self, need: int, device) -> None:
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != device:
+            # The arena is the caller's (C ABI): this host grows it with 6 % of headroom and drops the old one FIRST.  In an MD loop
+            # the edge count creeps up and down with every neighbour list; an arena sized exactly for the largest list so far is
+            # re-allocated at every new maximum, and a fresh 30-GB device allocation costs ~0.5 s on this stack (two such steps in
+            # the first 25 fs of the C4 run of tools/md_loop.py: profiles/r05_v22_md_loop_c4.json) while old + new briefly coexist.
+            self._workspace = None
+            self._workspace = torch.empty(need + need // 16 + (1 << 20), dtype=torch.uint8, device=device)
+
     def _energy_forces_on_device(self, lib, pos, graph, with_forces):
         self._select_device(pos.device)
         self._blocked = None  # (virial / atom_virial follow the kind of step that ran last)
         self._ensure_plan()
         self._ensure_weights(pos.device)
         N, E = graph.num_atoms, graph.num_edges
-        need = lib.lib.aa_model_workspace_bytes(self._plan_handle, N, E, int(with_forces))
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != pos.device:
-            # The arena is the caller's (C ABI): this host grows it with 6 % of headroom and drops the old one FIRST.  In an MD loop
-            # the edge count creeps up and down with every neighbour list; an arena sized exactly for the largest list so far is
-            # re-allocated at every new maximum, and a fresh 30-GB device allocation costs ~0.5 s on this stack (two such steps in
-            # the first 25 fs of the C4 run of tools/md_loop.py: profiles/r05_v22_md_loop_c4.json) while old + new briefly coexist.
-            self._workspace = None
-            self._workspace = torch.empty(need + need // 16 + (1 << 20), dtype=torch.uint8, device=pos.device)
+        self._ensure_workspace(lib.lib.aa_model_workspace_bytes(self._plan_handle, N, E, int(with_forces)), pos.device)
         pos = pos.detach().contiguous()
         if getattr(self, "_hip_graph", False):
             # replay mode: outputs live in persistent buffers so that every argument of the step keeps its address
@@ -1329,36 +1328,37 @@ class HipAllegroModel(torch.nn.Module):
         stream = torch.cuda.current_stream(dev).cuda_stream if dev is not None and dev.type == "cuda" else None
         lib.check(lib.lib.aa_model_check(self._plan_handle, stream), "aa_model_check")
 
-    def virial(self, graph: PreparedGraph) -> torch.Tensor:
-        """dE/d(strain) [3,3] of the LAST `energy_forces(..., with_forces=True)` call on `graph` (stress = virial / volume,
-        nequip ForceStressOutput; LAMMPS' virial is its negative)."""
+    def _after_step(self, what: str):
+        """(lib, cap) for an observable that reads what the last force step left in the workspace of the current device;
+        cap: `max_block_edges` of that step when it was a blocked one, None after an unblocked step."""
         lib = self._get_lib()
         if getattr(self, "_plan_handle", None) is None or self._workspace is None:
-            raise RuntimeError("virial reads what a step with forces left behind: call energy_forces first")
-        out = torch.empty(9, dtype=self.dtype, device=self._workspace.device)
-        g = graph.c_struct()
-        with _device_ctx(out.device):
-            return self._virial_on_device(lib, g, out)
-
-    def _blocked_cap_for(self, what: str) -> Optional[int]:
-        """`max_block_edges` of the blocked step the current device's workspace holds, None after an unblocked step."""
+            raise RuntimeError(f"{what} reads what a step with forces left behind: call energy_forces first")
         if self._blocked is None:
-            return None
+            return lib, None
         cap, with_forces = self._blocked
         if not with_forces:
             raise RuntimeError(f"{what} reads what a step with forces left behind, and the last step was a blocked energy-only one "
                                "(it keeps no frame-wide edge arrays): call energy_forces with forces first")
-        return cap
+        return lib, cap
 
-    def _virial_on_device(self, lib, g, out):
-        cap = self._blocked_cap_for("virial")
-        if cap is not None:  # the last step on this device was a blocked one
-            lib.check(lib.lib.aa_model_blocked_virial(self._plan_handle, C.byref(g), cap, self._workspace.data_ptr(), self._workspace.numel(),
-                                                      out.data_ptr(), _stream_ptr(out)), "aa_model_blocked_virial")
-            return out.view(3, 3)
-        lib.check(lib.lib.aa_model_virial(self._plan_handle, C.byref(g), self._workspace.data_ptr(), self._workspace.numel(),
-                                          out.data_ptr(), _stream_ptr(out)), "aa_model_virial")
-        return out.view(3, 3)
+    def _observable(self, step, name: str, graph: PreparedGraph, out: torch.Tensor, *args) -> torch.Tensor:
+        """`aa_model_<name>` into `out`, or `aa_model_blocked_<name>` (the cap behind the graph) when the last step was a blocked one;
+        `step`: what `_after_step` returned."""
+        lib, cap = step
+        fn = f"aa_model_{name}" if cap is None else f"aa_model_blocked_{name}"
+        g = graph.c_struct()
+        with _device_ctx(out.device):
+            lib.check(getattr(lib.lib, fn)(self._plan_handle, C.byref(g), *(() if cap is None else (cap,)), self._workspace.data_ptr(),
+                                           self._workspace.numel(), *args, out.data_ptr(), _stream_ptr(out)), fn)
+        return out
+
+    def virial(self, graph: PreparedGraph) -> torch.Tensor:
+        """dE/d(strain) [3,3] of the LAST `energy_forces(..., with_forces=True)` call on `graph` (stress = virial / volume,
+        nequip ForceStressOutput; LAMMPS' virial is its negative)."""
+        step = self._after_step("virial")
+        out = torch.empty(9, dtype=self.dtype, device=self._workspace.device)
+        return self._observable(step, "virial", graph, out).view(3, 3)
 
     _ATOM_VIRIAL = {"center": 0, "neighbor": 1, "split": 2}  # AA_ATOM_VIRIAL_*
 
@@ -1371,22 +1371,9 @@ class HipAllegroModel(torch.nn.Module):
         "split" need the graph's transposed CSR."""
         if attribution not in self._ATOM_VIRIAL:
             raise ValueError(f"attribution must be one of {sorted(self._ATOM_VIRIAL)}, not {attribution!r}")
-        lib = self._get_lib()
-        if getattr(self, "_plan_handle", None) is None or self._workspace is None:
-            raise RuntimeError("atom_virial reads what a step with forces left behind: call energy_forces first")
+        step = self._after_step("atom_virial")
         out = torch.empty((graph.num_atoms, 3, 3), dtype=self.dtype, device=self._workspace.device)
-        g = graph.c_struct()
-        cap = self._blocked_cap_for("atom_virial")
-        with _device_ctx(out.device):
-            if cap is not None:  # the last step on this device was a blocked one
-                lib.check(lib.lib.aa_model_blocked_atom_virial(self._plan_handle, C.byref(g), cap, self._workspace.data_ptr(),
-                                                               self._workspace.numel(), self._ATOM_VIRIAL[attribution], out.data_ptr(),
-                                                               _stream_ptr(out)), "aa_model_blocked_atom_virial")
-                return out
-            lib.check(lib.lib.aa_model_atom_virial(self._plan_handle, C.byref(g), self._workspace.data_ptr(), self._workspace.numel(),
-                                                   self._ATOM_VIRIAL[attribution], out.data_ptr(), _stream_ptr(out)),
-                      "aa_model_atom_virial")
-        return out
+        return self._observable(step, "atom_virial", graph, out, self._ATOM_VIRIAL[attribution])
 
     def heat_flux_potential(self, graph: PreparedGraph, velocities: torch.Tensor) -> torch.Tensor:
         """Potential part of the Green-Kubo heat flux [3] of the last step with forces on `graph`:
@@ -1395,22 +1382,10 @@ class HipAllegroModel(torch.nn.Module):
         One streaming reduction over the edges (`aa_model_heat_flux`): bit-reproducible, and the graph needs no transposed CSR."""
         if tuple(velocities.shape) != (graph.num_atoms, 3):
             raise ValueError(f"velocities must be [{graph.num_atoms}, 3], not {list(velocities.shape)}")
-        lib = self._get_lib()
-        if getattr(self, "_plan_handle", None) is None or self._workspace is None:
-            raise RuntimeError("heat_flux_potential reads what a step with forces left behind: call energy_forces first")
+        step = self._after_step("heat_flux_potential")
         vel = velocities.detach().to(device=self._workspace.device, dtype=self.dtype).contiguous()
         out = torch.empty(3, dtype=self.dtype, device=self._workspace.device)
-        g = graph.c_struct()
-        cap = self._blocked_cap_for("heat_flux_potential")
-        with _device_ctx(out.device):
-            if cap is not None:  # the last step on this device was a blocked one
-                lib.check(lib.lib.aa_model_blocked_heat_flux(self._plan_handle, C.byref(g), cap, self._workspace.data_ptr(),
-                                                             self._workspace.numel(), vel.data_ptr(), out.data_ptr(), _stream_ptr(out)),
-                          "aa_model_blocked_heat_flux")
-                return out
-            lib.check(lib.lib.aa_model_heat_flux(self._plan_handle, C.byref(g), self._workspace.data_ptr(), self._workspace.numel(),
-                                                 vel.data_ptr(), out.data_ptr(), _stream_ptr(out)), "aa_model_heat_flux")
-        return out
+        return self._observable(step, "heat_flux", graph, out, vel.data_ptr())
 
     def enable_hip_graph(self, on: bool = True) -> None:
         """Capture the step's launch sequence into a hipGraph and replay it (aa_model_plan_enable_graph): for

@@ -4,13 +4,16 @@ Used by `pytest -m "not gpu"` to exercise kernel logic without a GPU; never load
 """
 import os
 import subprocess
+import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "allegro_amd", "csrc")
 OUT_DIR = os.path.join(HERE, "_build")
 LIB = os.path.join(OUT_DIR, "liballegro_amd_emu.so")
-SOURCES = ["aa_gemm.hip", "aa_tp.hip", "aa_tp_spec.hip", "aa_tp_op.hip", "aa_tp_dense.hip", "aa_train.hip", "aa_edge.hip", "aa_fused.hip", "aa_fused8.hip", "aa_chain_res.hip", "aa_model.hip", "aa_nl.hip", "aa_hostfile.hip"]
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+from allegro_amd.build import SOURCES  # noqa: E402  (ONE list of sources: the product's)
 
 
 EXTRA = [d for d in os.environ.get("AA_EMU_DEFINES", "").split() if d]  # extra -D switches (debugging of kernel variants)
