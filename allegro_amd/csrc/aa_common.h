@@ -757,6 +757,28 @@ struct EdgeGeomArgs {
 template <typename T>
 int launch_edge_prologue(const EdgeGeomArgs& a, hipStream_t stream);
 
+// LDS of the two edge kernels as a function of the model's sizes alone (esize: bytes of the model dtype).  ONE function each, read by
+// the plan check (`check_edge_kernel_limits`: aa_model_plan_create refuses a configuration whose edge kernels cannot be launched,
+// before any step has written anything) and by the launch that sizes the kernel's LDS, so the two cannot drift.
+constexpr int kMaxBessel = 16;
+constexpr size_t kEdgePrologueLdsLimit = 64 * 1024;   // the default dynamic-LDS limit of a workgroup
+constexpr size_t kEdgeBackwardLdsLimit = 160 * 1024;  // the LDS of a CU (opt-in above 64 KB)
+__host__ __device__ inline int prologue_ldb(int B) { return B == 8 ? 12 : B + 1; }
+// *stage_sh: the block's harmonics go through LDS (edge_prologue_kernel<T, true>) -- whenever four workgroups per CU stay resident
+inline size_t edge_prologue_lds_bytes(size_t esize, int num_bessels, int S0, int l_max, bool* stage_sh) {
+  const size_t D = size_t(l_max + 1) * size_t(l_max + 1);
+  const size_t base = esize * (256 * size_t(prologue_ldb(num_bessels)) + size_t(num_bessels) * size_t(S0)) + sizeof(int) * 512;
+  const size_t staged = base + esize * 256 * D;
+  const bool stage = staged <= 40 * 1024;
+  if (stage_sh) *stage_sh = stage;
+  return stage ? staged : base;
+}
+inline size_t edge_backward_lds_bytes(size_t esize, int num_bessels, int S0, int num_types) {
+  return esize * (256 * size_t(num_bessels + 1) + size_t(kMaxBessel) * size_t(S0) + size_t(num_types) * size_t(S0)) + sizeof(int) * 256;
+}
+// AA_OK, or AA_ERR_INVALID naming the limit the sizes break
+int check_edge_kernel_limits(size_t esize, int num_bessels, int S0, int l_max, int num_types);
+
 struct EdgeBwdArgs {
   EdgeGeomArgs g;
   const void* g_emb0;  // [E,S0]

@@ -11,8 +11,6 @@
 
 namespace aa {
 
-__host__ __device__ inline int prologue_ldb(int B) { return B == 8 ? 12 : B + 1; }
-
 // STAGE_SH: the block's harmonics go through LDS and leave as one contiguous run (fp32 stacks: +9-16 KB of LDS);
 // without it every lane stores its own D values (large fp64 stacks, where the extra LDS would halve the occupancy)
 template <typename T, bool STAGE_SH>
@@ -695,16 +693,27 @@ __global__ __launch_bounds__(256) void readout_backward_kernel(ReadoutArgs a) {
   }
 }
 
+int check_edge_kernel_limits(size_t esize, int num_bessels, int S0, int l_max, int num_types) {
+  const size_t pro = edge_prologue_lds_bytes(esize, num_bessels, S0, l_max, nullptr);
+  if (pro > kEdgePrologueLdsLimit)
+    return fail(AA_ERR_INVALID, "model: the edge prologue needs " + std::to_string(pro) + " bytes of LDS for num_bessels = " + std::to_string(num_bessels) +
+                                    " and radial_chemical_embed_dim = " + std::to_string(S0) + ", more than the " + std::to_string(kEdgePrologueLdsLimit) +
+                                    " bytes of a workgroup");
+  const size_t bwd = edge_backward_lds_bytes(esize, num_bessels, S0, num_types);
+  if (bwd > kEdgeBackwardLdsLimit)
+    return fail(AA_ERR_INVALID, "model: the edge reverse needs " + std::to_string(bwd) + " bytes of LDS for " + std::to_string(num_types) +
+                                    " types and radial_chemical_embed_dim = " + std::to_string(S0) + ", more than the " +
+                                    std::to_string(kEdgeBackwardLdsLimit) + " bytes of a CU");
+  return AA_OK;
+}
+
 template <typename T>
 int launch_edge_prologue(const EdgeGeomArgs& a, hipStream_t stream) {
   if (a.E == 0) return AA_OK;
   AA_REQUIRE(a.num_bessels <= kMaxBessel && a.l_max >= 1 && a.l_max <= 3 && a.S0 % 2 == 0, "prologue: unsupported sizes");
-  const int D = (a.l_max + 1) * (a.l_max + 1);
-  const size_t base = sizeof(T) * (256 * size_t(prologue_ldb(a.num_bessels)) + size_t(a.num_bessels) * a.S0) + sizeof(int) * 512;
-  const size_t staged = base + sizeof(T) * 256 * size_t(D);
-  const bool stage = staged <= 40 * 1024;  // (four workgroups per CU stay resident)
-  const size_t smem = stage ? staged : base;
-  if (smem > 64 * 1024) return fail(AA_ERR_INVALID, "prologue: LDS tables too large");
+  bool stage = false;
+  const size_t smem = edge_prologue_lds_bytes(sizeof(T), a.num_bessels, a.S0, a.l_max, &stage);
+  if (smem > kEdgePrologueLdsLimit) return fail(AA_ERR_INVALID, "prologue: LDS tables too large");  // (refused at plan creation: check_edge_kernel_limits)
   if (stage)
     hipLaunchKernelGGL((edge_prologue_kernel<T, true>), dim3((unsigned)((a.E + 255) / 256)), dim3(256), smem, stream, a);
   else
@@ -716,8 +725,9 @@ int launch_edge_prologue(const EdgeGeomArgs& a, hipStream_t stream) {
 template <typename T>
 int launch_edge_backward(const EdgeBwdArgs& b, hipStream_t stream) {
   if (b.g.E == 0) return AA_OK;
-  size_t smem = sizeof(T) * (256 * size_t(b.g.num_bessels + 1) + size_t(kMaxBessel) * b.g.S0 + size_t(b.g.num_types) * b.g.S0) + sizeof(int) * 256;
-  if (smem > 160 * 1024) return fail(AA_ERR_INVALID, "edge_backward: too many types / embedding columns for the LDS tables");
+  const size_t smem = edge_backward_lds_bytes(sizeof(T), b.g.num_bessels, b.g.S0, b.g.num_types);
+  if (smem > kEdgeBackwardLdsLimit)  // (refused at plan creation: check_edge_kernel_limits)
+    return fail(AA_ERR_INVALID, "edge_backward: too many types / embedding columns for the LDS tables");
   if (smem > 64 * 1024)
     AA_CHECK_HIP(hipFuncSetAttribute((const void*)edge_backward_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, int(smem)));
   hipLaunchKernelGGL(edge_backward_kernel<T>, dim3((unsigned)((b.g.E + 255) / 256)), dim3(256), smem, stream, b);

@@ -82,8 +82,6 @@ __device__ __forceinline__ void cutoff_and_grad(T x, T p, T& f, T& df) {
   }
 }
 
-constexpr int kMaxBessel = 16;
-
 // spline basis of PerClassSpline._get_basis (allegro/nn/spline.py:81-89):
 //   b_s(x) = 0.25 (1 - cos(k (clamp(x, lo_s, lo_s + diff) - lo_s)))^2,  lo_s = (s - span)/n, diff = (span+1)/n, k = 2 pi/diff
 // value and d/dx (zero where the clamp is active)

@@ -826,11 +826,15 @@ static int validate_config(const aa_model_config* cfg) {
   AA_REQUIRE(cfg->embed_mlp_depth + 1 <= AA_MAX_MLP_LAYERS && cfg->latent_mlp_depth + 1 <= AA_MAX_MLP_LAYERS &&
                  cfg->readout_mlp_depth + 1 <= AA_MAX_MLP_LAYERS,
              "model: MLP too deep");
-  AA_REQUIRE(cfg->num_types > 0 && cfg->num_bessels > 0 && cfg->num_bessels <= 16 && cfg->embed_dim % 2 == 0,
-             "model: bad embedding sizes");
+  AA_REQUIRE(cfg->num_types > 0 && cfg->embed_dim % 2 == 0, "model: bad embedding sizes");
+  if (cfg->num_bessels < 1 || cfg->num_bessels > kMaxBessel)
+    return fail(AA_ERR_INVALID, "model: num_bessels / num_splines = " + std::to_string(cfg->num_bessels) + ", the edge kernels take 1.." +
+                                    std::to_string(kMaxBessel) + " radial basis functions");
   AA_REQUIRE(cfg->embed_kind == 0 || (cfg->embed_kind == 1 && cfg->spline_span >= 0 && cfg->spline_span <= cfg->num_bessels),
              "model: embed_kind must be 0 (Bessel) or 1 (spline, 0 <= span <= num_splines)");
-  return AA_OK;
+  // the LDS tables of the two edge kernels grow with the basis, the embedding width and the species count: a configuration they
+  // cannot be launched for is refused here, not by a launch helper behind a forward that has already written energies
+  return check_edge_kernel_limits(cfg->dtype == AA_F64 ? 8 : 4, cfg->num_bessels, cfg->embed_dim, cfg->l_max, cfg->num_types);
 }
 
 extern "C" int aa_model_plan_create(const aa_model_config* cfg, aa_model_plan** out) {

@@ -316,6 +316,12 @@ typedef struct {
                                  * persistent form with LDS-resident weights applies (round 6; A/B, tests)                               */
 } aa_plan_options;
 
+/* AA_ERR_INVALID, with aa_last_error() naming the limit and the size asked for, for a configuration whose edge kernels could not be
+ * launched: more than 16 radial basis functions (num_bessels: Bessel roots or splines), an edge prologue above 64 KB of LDS
+ * (esize (256 ldb + num_bessels embed_dim) + 2048 bytes, ldb = 12 for 8 basis functions and num_bessels + 1 otherwise; the launch
+ * adds esize 256 (l_max + 1)^2 bytes for the harmonics while the sum stays within 40 KB, which cannot reach the limit), an edge
+ * reverse above 160 KB (esize (256 (num_bessels + 1) + (16 + num_types) embed_dim) + 1024 bytes).  No step of an accepted plan is
+ * refused for these sizes afterwards. */
 int aa_model_plan_create(const aa_model_config* cfg, aa_model_plan** out);
 int aa_model_plan_create_with_options(const aa_model_config* cfg, const aa_plan_options* options, aa_model_plan** out);
 void aa_model_plan_destroy(aa_model_plan* plan);
