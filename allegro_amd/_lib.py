@@ -154,6 +154,17 @@ class EdgeList(C.Structure):
                 ("index_is_int64", C.c_int32), ("dtype", C.c_int32), ("pos", C.c_void_p), ("shift_vec", C.c_void_p)]
 
 
+class Frames(C.Structure):
+    """`aa_frames`: a batch of frames as device offsets into the atom order."""
+    _fields_ = [("num_frames", C.c_int32), ("frame_atoms", C.c_void_p)]
+
+
+class NlFramesInput(C.Structure):
+    """`aa_nl_frames_input`: positions of a batch, one DEVICE cell per frame (aa_nl_frames_*)."""
+    _fields_ = [("num_atoms", C.c_int64), ("pos", C.c_void_p), ("cells", C.c_void_p), ("pbc", C.c_int32 * 3), ("dtype", C.c_int32),
+                ("r_cut", C.c_double)]
+
+
 class AllegroLib:
     def __init__(self, cdll: C.CDLL, is_emulation: bool = False):
         self.lib = cdll
@@ -255,6 +266,22 @@ class AllegroLib:
             for fn, cap in ((f"aa_model_{name}", []), (f"aa_model_blocked_{name}", [C.c_int64])):
                 getattr(L, fn).argtypes = [C.c_void_p, C.POINTER(Graph)] + cap + [C.c_void_p, C.c_size_t] + mid + [C.c_void_p, C.c_void_p]
                 getattr(L, fn).restype = C.c_int
+        # the per-frame sums of a batch: the descriptor goes between the graph (and the cap) and the workspace
+        L.aa_model_frame_energies.argtypes = [C.c_void_p, C.POINTER(Frames), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.aa_model_frame_energies.restype = C.c_int
+        for name, mid in (("frame_virial", []), ("frame_heat_flux", [C.c_void_p])):
+            for fn, cap in ((f"aa_model_{name}", []), (f"aa_model_blocked_{name}", [C.c_int64])):
+                getattr(L, fn).argtypes = ([C.c_void_p, C.POINTER(Graph)] + cap + [C.POINTER(Frames), C.c_void_p, C.c_size_t] + mid +
+                                           [C.c_void_p, C.c_void_p])
+                getattr(L, fn).restype = C.c_int
+        L.aa_nl_frames_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+        L.aa_nl_frames_workspace_bytes.restype = C.c_size_t
+        L.aa_nl_frames_count.argtypes = [C.POINTER(NlFramesInput), C.POINTER(Frames), C.c_void_p, C.c_size_t, C.c_void_p,
+                                         C.POINTER(C.c_int64), C.c_void_p]
+        L.aa_nl_frames_count.restype = C.c_int
+        L.aa_nl_frames_fill.argtypes = [C.POINTER(NlFramesInput), C.POINTER(Frames), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.aa_nl_frames_fill.restype = C.c_int
         _i64p = C.POINTER(C.c_int64)
         L.aa_model_blocked_workspace_bytes.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int]
         L.aa_model_blocked_workspace_bytes.restype = C.c_size_t

@@ -835,6 +835,30 @@ struct HeatFluxArgs {
 };
 template <typename T>
 int launch_heat_flux(const HeatFluxArgs& a, hipStream_t stream);
+// Per-frame sums of a batch of frames (aa_frames): frame b owns the atoms [lo, hi) = clamped [frame_atoms[b], frame_atoms[b+1]) and, the
+// graph being center-sorted, the edges [rowptr[lo], rowptr[hi]).  ONE workgroup per frame, one launch, no scratch:
+//   FRAME_ENERGY  out[b]    = sum over the frame's atoms of x0[n]                               (K = 1)
+//   FRAME_VIRIAL  out[b][9] = the W of VirialArgs over the frame's edges (x0 = dvec, x1 = vec)   (K = 9)
+//   FRAME_FLUX    out[b][3] = the flux of HeatFluxArgs over the frame's edges                    (K = 3)
+// Sums in double, lane t of the workgroup takes the frame's elements t, t + 256, ... counted from the frame's own start, then the LDS
+// tree of block_tree_sum: a frame's bits depend on its own rows only.  Offsets the clamp had to change give a NaN row and
+// *status = kFrameStatusBase - b (host-visible; nullable).
+enum FrameSumKind { FRAME_ENERGY = 0, FRAME_VIRIAL = 1, FRAME_FLUX = 2 };
+struct FrameSumArgs {
+  int32_t B;
+  const int32_t* frame_atoms;  // [B+1] device
+  int64_t N, E;                // atoms / edges of the arrays below: the clamps
+  const int32_t* rowptr;       // [N+1]; not read by FRAME_ENERGY
+  const void *x0, *x1;         // FRAME_ENERGY: atom_energy [N], -; the edge sums: dvec [E,4], vec [E,4]
+  const int32_t* nbr;          // [E]   FRAME_FLUX only
+  const void* vel;             // [N,3] FRAME_FLUX only
+  int32_t* status;
+  void* out;                   // [B][K] model dtype
+};
+// the status word of a frame whose offsets were clamped: below every block code (-16 - block) a call can produce
+constexpr int32_t kFrameStatusBase = -(int32_t(1) << 30);
+template <typename T>
+int launch_frame_sum(FrameSumKind kind, const FrameSumArgs& a, hipStream_t stream);
 // verifies the aa_graph.atom_begin / atom_end promise (no edge segment outside the block): *status = -2 otherwise
 int launch_graph_hint_check(const int32_t* rowptr, int64_t N, int64_t a0, int64_t a1, int32_t* status, void* atom_energy, void* forces,
                             int esize, hipStream_t stream);

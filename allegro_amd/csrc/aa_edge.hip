@@ -737,8 +737,9 @@ int launch_edge_backward(const EdgeBwdArgs& b, hipStream_t stream) {
 
 // Fixed-order sum of K doubles per lane over the edges: the 256 lanes of a block through LDS (block_tree_sum), then one block over
 // the block partials in block order, rounded once (edge_sum_final_kernel).  No atomics: the same bits on every call.
+// (the tree itself: on return sP[0..K) holds the sums over the 256 lanes, visible to every lane -- shared with frame_sum_kernel)
 template <int K>
-__device__ inline void block_tree_sum(double* sP /* [256][K] */, const double (&w)[K], double* partial /* [gridDim.x][K] */) {
+__device__ inline void block_tree_reduce(double* sP /* [256][K] */, const double (&w)[K]) {
 #pragma unroll
   for (int k = 0; k < K; ++k) sP[threadIdx.x * K + k] = w[k];
   __syncthreads();
@@ -747,6 +748,10 @@ __device__ inline void block_tree_sum(double* sP /* [256][K] */, const double (&
       for (int k = 0; k < K; ++k) sP[threadIdx.x * K + k] += sP[(threadIdx.x + st) * K + k];
     __syncthreads();
   }
+}
+template <int K>
+__device__ inline void block_tree_sum(double* sP /* [256][K] */, const double (&w)[K], double* partial /* [gridDim.x][K] */) {
+  block_tree_reduce<K>(sP, w);
   if (threadIdx.x < K) partial[blockIdx.x * K + threadIdx.x] = sP[threadIdx.x];
 }
 template <typename T, int K, bool NEGATE>
@@ -817,6 +822,87 @@ int launch_heat_flux(const HeatFluxArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL((edge_sum_final_kernel<T, 3, true>), dim3(1), dim3(64), 0, stream, a.partial, nb, a.out);
   AA_CHECK_HIP(hipGetLastError());
   return AA_OK;
+}
+
+// ---- per-frame sums of a batch (FrameSumArgs): one kernel over a per-element body with K accumulators.  A body says what its
+// ---- elements are (atoms, or the edges of the frame's atoms), adds element i into w, and whether the sum is negated.
+template <typename T>
+struct FrameEnergyBody {
+  static constexpr int K = 1;
+  static constexpr bool EDGES = false, NEGATE = false;
+  static __device__ __forceinline__ void add(const FrameSumArgs& a, int64_t n, double (&w)[1]) { w[0] += double(static_cast<const T*>(a.x0)[n]); }
+};
+template <typename T>
+struct FrameVirialBody {  // the products of atom_virial_edge: rows loaded whole
+  static constexpr int K = 9;
+  static constexpr bool EDGES = true, NEGATE = false;
+  static __device__ __forceinline__ void add(const FrameSumArgs& a, int64_t e, double (&w)[9]) {
+    atom_virial_edge<T>(static_cast<const T*>(a.x0), static_cast<const T*>(a.x1), e, 1.0, w);
+  }
+};
+template <typename T>
+struct FrameFluxBody {  // the products of heat_flux_partial_kernel
+  static constexpr int K = 3;
+  static constexpr bool EDGES = true, NEGATE = true;
+  static __device__ __forceinline__ void add(const FrameSumArgs& a, int64_t e, double (&w)[3]) {
+    typedef T V4 __attribute__((ext_vector_type(4)));
+    const V4 d = *reinterpret_cast<const V4*>(static_cast<const T*>(a.x0) + 4 * e);
+    const V4 v = *reinterpret_cast<const V4*>(static_cast<const T*>(a.x1) + 4 * e);
+    const T* u = static_cast<const T*>(a.vel) + 3 * int64_t(a.nbr[e]);
+    const double p = double(d[0]) * double(u[0]) + double(d[1]) * double(u[1]) + double(d[2]) * double(u[2]);  // g_e . v_j(e)
+    const double r = double(v[3]);
+    w[0] += double(v[0]) * r * p;
+    w[1] += double(v[1]) * r * p;
+    w[2] += double(v[2]) * r * p;
+  }
+};
+
+__device__ __forceinline__ int64_t clamp_i64(int64_t x, int64_t lo, int64_t hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+// One workgroup per frame.  The offsets live on the device, so they are clamped here -- lo into [0, N], hi into [lo, N], the row
+// pointers of an edge body into [0, E] -- and no index leaves the arrays whatever the descriptor holds; a frame whose offsets the
+// clamp changed gets a NaN row and raises the status word (any one of several such frames is the one reported).  Lane t takes the
+// elements t, t + 256, ... counted from the frame's own first element, so the sum does not depend on where the frame lies in the batch.
+template <typename T, typename Body>
+__global__ __launch_bounds__(256) void frame_sum_kernel(FrameSumArgs a) {
+  constexpr int K = Body::K;
+  double* sP = reinterpret_cast<double*>(aa_smem);  // [256][K]
+  const int b = blockIdx.x;
+  const int64_t f0 = a.frame_atoms[b], f1 = a.frame_atoms[b + 1];
+  const int64_t lo = clamp_i64(f0, 0, a.N), hi = clamp_i64(f1, lo, a.N);
+  const bool bad = lo != f0 || hi != f1;
+  int64_t i0 = lo, i1 = hi;
+  if constexpr (Body::EDGES) {
+    i0 = clamp_i64(a.rowptr[lo], 0, a.E);
+    i1 = clamp_i64(a.rowptr[hi], i0, a.E);
+  }
+  double w[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) w[k] = 0.0;
+  for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) Body::add(a, i, w);
+  block_tree_reduce<K>(sP, w);
+  if (threadIdx.x < K) {
+    const double s = sP[threadIdx.x];
+    T* o = static_cast<T*>(a.out) + int64_t(b) * K + threadIdx.x;
+    if (bad) *o = T(__builtin_nan(""));
+    else *o = Body::NEGATE ? T(0.0 - s) : T(s);  // (0.0 - s: an empty frame gives +0)
+  }
+  if (bad && threadIdx.x == 0 && a.status) *reinterpret_cast<volatile int32_t*>(a.status) = kFrameStatusBase - (b < (1 << 30) - 1 ? b : (1 << 30) - 1);
+}
+template <typename T, typename Body>
+static int launch_frame_body(const FrameSumArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL((frame_sum_kernel<T, Body>), dim3((unsigned)a.B), dim3(256), sizeof(double) * 256 * Body::K, stream, a);
+  AA_CHECK_HIP(hipGetLastError());
+  return AA_OK;
+}
+template <typename T>
+int launch_frame_sum(FrameSumKind kind, const FrameSumArgs& a, hipStream_t stream) {
+  if (a.B <= 0) return AA_OK;
+  switch (kind) {
+    case FRAME_ENERGY: return launch_frame_body<T, FrameEnergyBody<T>>(a, stream);
+    case FRAME_VIRIAL: return launch_frame_body<T, FrameVirialBody<T>>(a, stream);
+    default: return launch_frame_body<T, FrameFluxBody<T>>(a, stream);
+  }
 }
 
 template <typename T>
@@ -924,6 +1010,7 @@ int launch_readout_backward(const ReadoutArgs& a, hipStream_t stream) {
   template int launch_virial<T>(const VirialArgs&, hipStream_t);               \
   template int launch_atom_virial<T>(const AtomVirialArgs&, hipStream_t);      \
   template int launch_heat_flux<T>(const HeatFluxArgs&, hipStream_t);          \
+  template int launch_frame_sum<T>(FrameSumKind, const FrameSumArgs&, hipStream_t); \
   template int launch_pair_zbl<T>(const PairZblArgs&, hipStream_t);            \
   template int launch_readout_reduce<T>(const ReadoutArgs&, hipStream_t);      \
   template int launch_readout_backward<T>(const ReadoutArgs&, hipStream_t);

@@ -793,7 +793,8 @@ struct aa_model_plan {
   // whose graph contradicts the caller's hints (aa_graph.max_degree, atom_begin / atom_end) sets it, the offending atoms'
   // energies become NaN, and the NEXT aa_model_energy_forces on the plan -- or aa_model_check, which synchronises first --
   // returns AA_ERR_INVALID.  > 0: degree of a center atom beyond max_degree; -2: edges outside [atom_begin, atom_end);
-  // <= -16: block -16 - v of a blocked step was cut at the wrong edge.
+  // <= -16: block -16 - v of a blocked step was cut at the wrong edge; <= kFrameStatusBase: frame kFrameStatusBase - v of a per-frame
+  // sum (aa_model_frame_*) had offsets the kernel had to clamp.
   int32_t* status = nullptr;
 };
 
@@ -806,10 +807,13 @@ static int consume_status(const aa_model_plan* plan, const char* who) {
   if (*reinterpret_cast<volatile int32_t*>(plan->status) == 0) return AA_OK;
   const int32_t v = __atomic_exchange_n(plan->status, 0, __ATOMIC_ACQ_REL);
   if (v == 0) return AA_OK;
-  char msg[256];
+  char msg[384];
   if (v > 0)
     snprintf(msg, sizeof msg, "%s: a step on this plan met a center atom with %d edges, more than aa_graph.max_degree promised "
              "(its energy was set to NaN; pass the true maximum, or 0 for \"unknown\")", who, int(v));
+  else if (v <= kFrameStatusBase)
+    snprintf(msg, sizeof msg, "%s: a per-frame sum on this plan was given offsets outside [0, num_atoms] or decreasing for frame %d: "
+             "aa_frames.frame_atoms[b] / frame_atoms[b + 1] were clamped (that frame's row was set to NaN)", who, int(kFrameStatusBase - v));
   else if (v <= -16)
     snprintf(msg, sizeof msg, "%s: a blocked step on this plan was given a wrong cut for block %d: block_edges[b] / block_edges[b + 1] are not "
              "rowptr[block_atoms[b]] / rowptr[block_atoms[b + 1]] (energies and forces of the frame were set to NaN)", who, int(-16 - v));
@@ -3189,6 +3193,36 @@ int heat_flux_from(const aa_model_plan* plan, const aa_graph* graph, const char*
   hipStream_t s = static_cast<hipStream_t>(stream);
   return plan->cfg.dtype == AA_F32 ? launch_heat_flux<float>(a, s) : launch_heat_flux<double>(a, s);
 }
+
+// The per-frame sums of a batch (aa_frames): what the host can check of the descriptor, then one launch.  The edge sums find their
+// rows as the bodies above do; their scratch is not used.
+int check_frames(const aa_frames* frames, const char* who) {
+  AA_REQUIRE(frames, std::string(who) + ": null frames");
+  AA_REQUIRE(frames->num_frames >= 0, std::string(who) + ": negative num_frames");
+  AA_REQUIRE(frames->frame_atoms || frames->num_frames == 0, std::string(who) + ": null frame_atoms");
+  return AA_OK;
+}
+
+int frame_sum(const aa_model_plan* plan, FrameSumKind kind, const FrameSumArgs& a, aa_stream stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return plan->cfg.dtype == AA_F32 ? launch_frame_sum<float>(kind, a, s) : launch_frame_sum<double>(kind, a, s);
+}
+
+int frame_edge_sum_from(const aa_model_plan* plan, const aa_graph* graph, const aa_frames* frames, FrameSumKind kind, const char* who,
+                        int64_t max_block_edges, void* workspace, size_t workspace_bytes, const void* velocities, void* out, aa_stream stream) {
+  if (int rc = check_frames(frames, who)) return rc;
+  StepRows r;
+  if (int rc = locate_step_rows(plan, graph, max_block_edges, workspace, workspace_bytes, who, &r)) return rc;
+  if (!out && frames->num_frames > 0) return fail(AA_ERR_INVALID, std::string(who) + ": null output");
+  if (!graph->rowptr) return fail(AA_ERR_INVALID, std::string(who) + ": null row pointers (aa_graph.rowptr)");
+  if (kind == FRAME_FLUX) {
+    if (!velocities && graph->num_atoms > 0) return fail(AA_ERR_INVALID, std::string(who) + ": null velocities");
+    if (graph->num_edges > 0 && !graph->nbr) return fail(AA_ERR_INVALID, std::string(who) + ": null neighbor array (aa_graph.nbr)");
+  }
+  FrameSumArgs a{frames->num_frames, frames->frame_atoms, graph->num_atoms, graph->num_edges, graph->rowptr, r.dvec, r.vec, graph->nbr,
+                 velocities, plan->status, out};
+  return frame_sum(plan, kind, a, stream);
+}
 }  // namespace
 
 // The entry points: null checks, the blocked ones refuse a negative max_block_edges, then the body.
@@ -3230,6 +3264,47 @@ extern "C" int aa_model_blocked_heat_flux(const aa_model_plan* plan, const aa_gr
   AA_REQUIRE(plan && graph && workspace, "aa_model_blocked_heat_flux: null argument");
   AA_REQUIRE(max_block_edges >= 0, "aa_model_blocked_heat_flux: negative max_block_edges");
   return heat_flux_from(plan, graph, "aa_model_blocked_heat_flux", max_block_edges, workspace, workspace_bytes, velocities, flux3, stream);
+}
+
+extern "C" int aa_model_frame_energies(const aa_model_plan* plan, const aa_frames* frames, int64_t num_atoms, const void* atom_energy,
+                                       void* out_b, aa_stream stream) {
+  const char* who = "aa_model_frame_energies";
+  AA_REQUIRE(plan, "aa_model_frame_energies: null plan");
+  if (int rc = check_frames(frames, who)) return rc;
+  AA_REQUIRE(num_atoms >= 0, "aa_model_frame_energies: negative num_atoms");
+  AA_REQUIRE(atom_energy || num_atoms == 0, "aa_model_frame_energies: null atom_energy");
+  AA_REQUIRE(out_b || frames->num_frames == 0, "aa_model_frame_energies: null output");
+  FrameSumArgs a{frames->num_frames, frames->frame_atoms, num_atoms, 0, nullptr, atom_energy, nullptr, nullptr, nullptr, plan->status, out_b};
+  return frame_sum(plan, FRAME_ENERGY, a, stream);
+}
+
+extern "C" int aa_model_frame_virial(const aa_model_plan* plan, const aa_graph* graph, const aa_frames* frames, void* workspace,
+                                     size_t workspace_bytes, void* out_b9, aa_stream stream) {
+  AA_REQUIRE(plan && graph && workspace, "aa_model_frame_virial: null argument");
+  return frame_edge_sum_from(plan, graph, frames, FRAME_VIRIAL, "aa_model_frame_virial", -1, workspace, workspace_bytes, nullptr, out_b9, stream);
+}
+
+extern "C" int aa_model_blocked_frame_virial(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges, const aa_frames* frames,
+                                             void* workspace, size_t workspace_bytes, void* out_b9, aa_stream stream) {
+  AA_REQUIRE(plan && graph && workspace, "aa_model_blocked_frame_virial: null argument");
+  AA_REQUIRE(max_block_edges >= 0, "aa_model_blocked_frame_virial: negative max_block_edges");
+  return frame_edge_sum_from(plan, graph, frames, FRAME_VIRIAL, "aa_model_blocked_frame_virial", max_block_edges, workspace, workspace_bytes,
+                             nullptr, out_b9, stream);
+}
+
+extern "C" int aa_model_frame_heat_flux(const aa_model_plan* plan, const aa_graph* graph, const aa_frames* frames, void* workspace,
+                                        size_t workspace_bytes, const void* velocities, void* out_b3, aa_stream stream) {
+  AA_REQUIRE(plan && graph && workspace, "aa_model_frame_heat_flux: null argument");
+  return frame_edge_sum_from(plan, graph, frames, FRAME_FLUX, "aa_model_frame_heat_flux", -1, workspace, workspace_bytes, velocities, out_b3, stream);
+}
+
+extern "C" int aa_model_blocked_frame_heat_flux(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges,
+                                                const aa_frames* frames, void* workspace, size_t workspace_bytes, const void* velocities,
+                                                void* out_b3, aa_stream stream) {
+  AA_REQUIRE(plan && graph && workspace, "aa_model_blocked_frame_heat_flux: null argument");
+  AA_REQUIRE(max_block_edges >= 0, "aa_model_blocked_frame_heat_flux: negative max_block_edges");
+  return frame_edge_sum_from(plan, graph, frames, FRAME_FLUX, "aa_model_blocked_frame_heat_flux", max_block_edges, workspace, workspace_bytes,
+                             velocities, out_b3, stream);
 }
 
 extern "C" int aa_model_debug_tap(const aa_model_plan* plan, const char* name, int64_t N, int64_t E, const void* workspace,

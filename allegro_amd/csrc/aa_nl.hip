@@ -636,6 +636,309 @@ extern "C" int aa_nl_fill_typed(const aa_nl_input* in, const aa_nl_types* types,
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// aa_nl_frames_*: the list of a batch of small frames, every frame in its own cell.  No cell grid: one wave per centre atom walks
+// the atoms of its frame, 64 per pass, once per periodic image.  A listed pair's position is rowptr[centre] + its rank among the
+// listed pairs of the segment: an inclusive prefix sum over the lanes plus the pairs of the earlier passes (the shuffle form of
+// prune_kernel, which also runs in the CPU emulation build).  No atomic decides a position: images ascending, then neighbour id.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kNoBadFrame = 0x7fffffff;
+enum { FRAME_BAD_OFFSETS = 0, FRAME_BAD_SINGULAR = 1, FRAME_BAD_IMAGES = 2 };  // *bad = 4 * frame + reason of the FIRST refused frame
+
+struct NlFramesDev {
+  int64_t N;
+  int B;
+  const void* pos;
+  const double* cells;         // [B,9] the caller's
+  const int32_t* frame_atoms;  // [B+1] the caller's
+  int pbc[3];
+  double r_cut, rc2;
+  // workspace
+  double* inv;      // [B][9]
+  int* kimg;        // [B][3]
+  int* range;       // [B][2] the clamped atom range
+  int* reason;      // [B] -1, or why the frame is refused
+  int* atom_frame;  // [N] (-1: in no frame)
+  int* wrap;        // [N][3]
+  double* wpos;     // [N][3]
+  int* counts;      // [N+1]
+  int* scan_tmp;    // [N / 4096 + 2]
+  int* bad;         // kNoBadFrame, or 4 * frame + reason
+};
+
+// one thread per frame
+__global__ __launch_bounds__(256) void nlf_setup_kernel(NlFramesDev d) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= d.B) return;
+  const int64_t f0 = d.frame_atoms[b], f1 = d.frame_atoms[b + 1];
+  const int64_t lo = f0 < 0 ? 0 : (f0 > d.N ? d.N : f0);
+  const int64_t hi = f1 < lo ? lo : (f1 > d.N ? d.N : f1);
+  int reason = (lo != f0 || hi != f1) ? FRAME_BAD_OFFSETS : -1;
+  const double* c = d.cells + 9 * int64_t(b);
+  const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
+  double inv[9];
+  int k[3] = {0, 0, 0};
+  if (!(fabs(det) > 1e-12)) {  // (a NaN lands here too)
+    if (reason < 0) reason = FRAME_BAD_SINGULAR;
+    for (int q = 0; q < 9; ++q) inv[q] = 0.0;
+  } else {
+    // inverse (pos = s @ cell  =>  s = pos @ inv), as plan_nl
+    inv[0] = (c[4] * c[8] - c[5] * c[7]) / det;
+    inv[1] = (c[2] * c[7] - c[1] * c[8]) / det;
+    inv[2] = (c[1] * c[5] - c[2] * c[4]) / det;
+    inv[3] = (c[5] * c[6] - c[3] * c[8]) / det;
+    inv[4] = (c[0] * c[8] - c[2] * c[6]) / det;
+    inv[5] = (c[2] * c[3] - c[0] * c[5]) / det;
+    inv[6] = (c[3] * c[7] - c[4] * c[6]) / det;
+    inv[7] = (c[1] * c[6] - c[0] * c[7]) / det;
+    inv[8] = (c[0] * c[4] - c[1] * c[3]) / det;
+    for (int a = 0; a < 3; ++a) {
+      // perpendicular height along lattice direction a = 1 / |column a of inv|; wrapped atoms differ by less than one cell along a,
+      // so an image |n| > r_cut / h cannot hold a pair
+      const double n2 = inv[a] * inv[a] + inv[3 + a] * inv[3 + a] + inv[6 + a] * inv[6 + a];
+      const double images = d.pbc[a] ? ceil(d.r_cut * sqrt(n2) - 1e-12) : 0.0;
+      if (!(images <= 64.0)) {
+        if (reason < 0) reason = FRAME_BAD_IMAGES;
+      } else {
+        k[a] = int(images);
+      }
+    }
+  }
+  if (reason >= 0) k[0] = k[1] = k[2] = 0;
+  d.reason[b] = reason;
+  for (int q = 0; q < 9; ++q) d.inv[9 * int64_t(b) + q] = inv[q];
+  for (int a = 0; a < 3; ++a) d.kimg[3 * b + a] = k[a];
+  d.range[2 * b] = int(lo);
+  d.range[2 * b + 1] = int(hi);
+  for (int64_t i = lo; i < hi; ++i) d.atom_frame[i] = b;
+}
+
+// one workgroup: the first refused frame, by a minimum over the frames (no atomic: the same answer on every call)
+__global__ __launch_bounds__(256) void nlf_first_bad_kernel(NlFramesDev d) {
+  int* sMin = reinterpret_cast<int*>(aa_smem);  // [256]
+  int first = kNoBadFrame;
+  for (int b = threadIdx.x; b < d.B; b += 256)
+    if (d.reason[b] >= 0 && first == kNoBadFrame) first = 4 * b + d.reason[b];
+  sMin[threadIdx.x] = first;
+  __syncthreads();
+  for (int st = 128; st >= 1; st >>= 1) {
+    if (int(threadIdx.x) < st && sMin[threadIdx.x + st] < sMin[threadIdx.x]) sMin[threadIdx.x] = sMin[threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *d.bad = sMin[0];
+}
+
+// one thread per atom: the position wrapped into the cell of its frame along periodic directions (the arithmetic of nl_bin_kernel)
+template <typename T>
+__global__ __launch_bounds__(256) void nlf_wrap_kernel(NlFramesDev d) {
+  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= d.N) return;
+  const T* p = static_cast<const T*>(d.pos) + 3 * i;
+  const double x = double(p[0]), y = double(p[1]), z = double(p[2]);
+  int f = d.atom_frame[i];
+  f = f < 0 || f >= d.B ? -1 : f;
+  int w[3] = {0, 0, 0};
+  double cx = 0.0, cy = 0.0, cz = 0.0;
+  if (f >= 0) {
+    const double* inv = d.inv + 9 * int64_t(f);
+    const double* c = d.cells + 9 * int64_t(f);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      double s = x * inv[0 * 3 + a] + y * inv[1 * 3 + a] + z * inv[2 * 3 + a];
+      if (d.pbc[a] && s == s && fabs(s) < 1e9) {  // (a position that is not a number, or absurdly far away, is left where it is)
+        const double fl = floor(s);
+        w[a] = -int(fl);
+        s -= fl;
+        if (s >= 1.0) w[a] -= 1;  // rounding: -1e-17 - floor(.) == 1.0
+      }
+    }
+    cx = w[0] * c[0] + w[1] * c[3] + w[2] * c[6];
+    cy = w[0] * c[1] + w[1] * c[4] + w[2] * c[7];
+    cz = w[0] * c[2] + w[1] * c[5] + w[2] * c[8];
+  }
+  d.wpos[3 * i + 0] = x + cx;
+  d.wpos[3 * i + 1] = y + cy;
+  d.wpos[3 * i + 2] = z + cz;
+  d.wrap[3 * i + 0] = w[0];
+  d.wrap[3 * i + 1] = w[1];
+  d.wrap[3 * i + 2] = w[2];
+}
+
+// One wave per centre atom, four per workgroup.  Count (FILL = false) and fill are the same code: the same predicate in the same
+// double arithmetic, so rowptr always matches what fill writes.  After a count that raised the flag, fill writes nothing.
+template <typename T, bool FILL>
+__global__ __launch_bounds__(256) void nlf_pairs_kernel(NlFramesDev d, const int32_t* rowptr, int32_t* center, int32_t* nbr,
+                                                        int32_t* cell_shift, void* shift_vec) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (i >= d.N) return;  // (wave-uniform: every lane of a wave takes part in every exchange below)
+  const bool refused = *d.bad != kNoBadFrame;
+  int f = d.atom_frame[i];
+  f = f < 0 || f >= d.B ? -1 : f;
+  if (refused || f < 0) {
+    if (!FILL && lane == 0) d.counts[i] = 0;
+    return;
+  }
+  const int lo = d.range[2 * f], hi = d.range[2 * f + 1];
+  const int k0 = d.kimg[3 * f], k1 = d.kimg[3 * f + 1], k2 = d.kimg[3 * f + 2];
+  const double* c = d.cells + 9 * int64_t(f);
+  const double xi = d.wpos[3 * i], yi = d.wpos[3 * i + 1], zi = d.wpos[3 * i + 2];
+  const int wi0 = d.wrap[3 * i], wi1 = d.wrap[3 * i + 1], wi2 = d.wrap[3 * i + 2];
+  int64_t o = FILL ? rowptr[i] : 0;  // where this pass's first pair goes
+  int cnt = 0;
+  for (int n0 = -k0; n0 <= k0; ++n0)
+    for (int n1 = -k1; n1 <= k1; ++n1)
+      for (int n2 = -k2; n2 <= k2; ++n2) {
+        const double sx = n0 * c[0] + n1 * c[3] + n2 * c[6];
+        const double sy = n0 * c[1] + n1 * c[4] + n2 * c[7];
+        const double sz = n0 * c[2] + n1 * c[5] + n2 * c[8];
+        const bool home = n0 == 0 && n1 == 0 && n2 == 0;
+        for (int j0 = lo; j0 < hi; j0 += 64) {
+          const int j = j0 + lane;
+          bool listed = j < hi && !(home && j == i);
+          if (listed) {
+            const double dx = d.wpos[3 * int64_t(j)] + sx - xi, dy = d.wpos[3 * int64_t(j) + 1] + sy - yi,
+                         dz = d.wpos[3 * int64_t(j) + 2] + sz - zi;
+            listed = dx * dx + dy * dy + dz * dz < d.rc2;
+          }
+          if constexpr (FILL) {
+            int x = listed ? 1 : 0;
+            for (int st = 1; st < 64; st <<= 1) {
+              const int y = __shfl_up(x, st);
+              if (lane >= st) x += y;
+            }
+            if (listed) {
+              const int64_t e = o + x - 1;
+              center[e] = int32_t(i);
+              nbr[e] = j;
+              // undo the wrapping: r_e = pos[j] - pos[i] + S @ cell with S = n + w_j - w_i
+              const int S0 = n0 + d.wrap[3 * int64_t(j)] - wi0, S1 = n1 + d.wrap[3 * int64_t(j) + 1] - wi1,
+                        S2 = n2 + d.wrap[3 * int64_t(j) + 2] - wi2;
+              if (cell_shift) {
+                cell_shift[3 * e] = S0;
+                cell_shift[3 * e + 1] = S1;
+                cell_shift[3 * e + 2] = S2;
+              }
+              if (shift_vec) {
+                T* sv = static_cast<T*>(shift_vec) + 3 * e;
+                sv[0] = T(S0 * c[0] + S1 * c[3] + S2 * c[6]);
+                sv[1] = T(S0 * c[1] + S1 * c[4] + S2 * c[7]);
+                sv[2] = T(S0 * c[2] + S1 * c[5] + S2 * c[8]);
+              }
+            }
+            o += __shfl(x, 63);
+          } else {
+            cnt += listed ? 1 : 0;
+          }
+        }
+      }
+  if constexpr (!FILL) {
+    for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m);
+    if (lane == 0) d.counts[i] = cnt;
+  }
+}
+
+int plan_nl_frames(const aa_nl_frames_input* in, const aa_frames* frames, void* ws, size_t ws_bytes, const char* who, NlFramesDev& d) {
+  const std::string w(who);
+  AA_REQUIRE(in && frames && ws, w + ": null argument");
+  AA_REQUIRE(in->num_atoms >= 0 && in->num_atoms < (int64_t(1) << 31), w + ": atom count out of range");
+  AA_REQUIRE(frames->num_frames >= 0 && frames->num_frames < (1 << 29), w + ": num_frames out of range");
+  AA_REQUIRE(in->dtype == AA_F32 || in->dtype == AA_F64, w + ": bad dtype");
+  AA_REQUIRE(in->r_cut > 0.0 && std::isfinite(in->r_cut), w + ": r_cut must be positive and finite");
+  AA_REQUIRE(in->pos || in->num_atoms == 0, w + ": null positions");
+  AA_REQUIRE((frames->frame_atoms && in->cells) || frames->num_frames == 0, w + ": null frame_atoms or cells");
+  if (ws_bytes < aa_nl_frames_workspace_bytes(in->num_atoms, frames->num_frames)) return fail(AA_ERR_WORKSPACE, w + ": workspace too small");
+  d.N = in->num_atoms;
+  d.B = frames->num_frames;
+  d.pos = in->pos;
+  d.cells = in->cells;
+  d.frame_atoms = frames->frame_atoms;
+  for (int a = 0; a < 3; ++a) d.pbc[a] = in->pbc[a] ? 1 : 0;
+  d.r_cut = in->r_cut;
+  d.rc2 = in->r_cut * in->r_cut;
+  char* base = static_cast<char*>(ws);
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    char* r = base + o;
+    o += align_up(bytes);
+    return r;
+  };
+  const size_t N = size_t(d.N), B = size_t(d.B);
+  d.inv = reinterpret_cast<double*>(take(sizeof(double) * 9 * B));
+  d.wpos = reinterpret_cast<double*>(take(sizeof(double) * 3 * N));
+  d.kimg = reinterpret_cast<int*>(take(sizeof(int) * 3 * B));
+  d.range = reinterpret_cast<int*>(take(sizeof(int) * 2 * B));
+  d.reason = reinterpret_cast<int*>(take(sizeof(int) * B));
+  d.atom_frame = reinterpret_cast<int*>(take(sizeof(int) * N));
+  d.wrap = reinterpret_cast<int*>(take(sizeof(int) * 3 * N));
+  d.counts = reinterpret_cast<int*>(take(sizeof(int) * (N + 1)));
+  d.scan_tmp = reinterpret_cast<int*>(take(sizeof(int) * (N / kScanBlock + 2)));
+  d.bad = reinterpret_cast<int*>(take(sizeof(int)));
+  return AA_OK;
+}
+
+}  // namespace
+
+extern "C" size_t aa_nl_frames_workspace_bytes(int64_t num_atoms, int32_t num_frames) {
+  const size_t N = size_t(std::max<int64_t>(0, num_atoms)), B = size_t(std::max<int32_t>(0, num_frames));
+  return align_up(sizeof(double) * 9 * B) + align_up(sizeof(double) * 3 * N) + align_up(sizeof(int) * 3 * B) + align_up(sizeof(int) * 2 * B) +
+         align_up(sizeof(int) * B) + align_up(sizeof(int) * N) + align_up(sizeof(int) * 3 * N) + align_up(sizeof(int) * (N + 1)) +
+         align_up(sizeof(int) * (N / kScanBlock + 2)) + align_up(sizeof(int));
+}
+
+extern "C" int aa_nl_frames_count(const aa_nl_frames_input* in, const aa_frames* frames, void* workspace, size_t workspace_bytes,
+                                  int32_t* rowptr, int64_t* num_edges, aa_stream stream) {
+  NlFramesDev d{};
+  if (int rc = plan_nl_frames(in, frames, workspace, workspace_bytes, "aa_nl_frames_count", d)) return rc;
+  AA_REQUIRE(rowptr && num_edges, "aa_nl_frames_count: null output");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (d.N > 0) AA_CHECK_HIP(hipMemsetAsync(d.atom_frame, 0xff, sizeof(int) * size_t(d.N), s));  // -1: in no frame
+  if (d.B > 0) hipLaunchKernelGGL(nlf_setup_kernel, dim3((d.B + 255) / 256), dim3(256), 0, s, d);
+  hipLaunchKernelGGL(nlf_first_bad_kernel, dim3(1), dim3(256), sizeof(int) * 256, s, d);
+  if (d.N > 0) {
+    const dim3 atoms((unsigned)((d.N + 255) / 256)), waves((unsigned)((d.N + 3) / 4));
+    if (in->dtype == AA_F32) {
+      hipLaunchKernelGGL(nlf_wrap_kernel<float>, atoms, dim3(256), 0, s, d);
+      hipLaunchKernelGGL((nlf_pairs_kernel<float, false>), waves, dim3(256), 0, s, d, nullptr, nullptr, nullptr, nullptr, nullptr);
+    } else {
+      hipLaunchKernelGGL(nlf_wrap_kernel<double>, atoms, dim3(256), 0, s, d);
+      hipLaunchKernelGGL((nlf_pairs_kernel<double, false>), waves, dim3(256), 0, s, d, nullptr, nullptr, nullptr, nullptr, nullptr);
+    }
+  }
+  launch_scan(d.counts, rowptr, d.N, d.scan_tmp, s);
+  AA_CHECK_HIP(hipGetLastError());
+  int32_t total = 0, bad = kNoBadFrame;
+  AA_CHECK_HIP(hipMemcpyAsync(&total, rowptr + d.N, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  AA_CHECK_HIP(hipMemcpyAsync(&bad, d.bad, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  AA_CHECK_HIP(hipStreamSynchronize(s));
+  if (bad != kNoBadFrame) {
+    static const char* const why[] = {"frame_atoms outside [0, num_atoms] or decreasing", "singular cell",
+                                      "cell much smaller than r_cut (more than 64 images along one direction)", "?"};
+    return fail(AA_ERR_INVALID, "aa_nl_frames_count: frame " + std::to_string(bad / 4) + ": " + why[bad % 4]);
+  }
+  AA_REQUIRE(total >= 0, "aa_nl_frames_count: more than 2^31 edges");
+  *num_edges = total;
+  return AA_OK;
+}
+
+extern "C" int aa_nl_frames_fill(const aa_nl_frames_input* in, const aa_frames* frames, void* workspace, size_t workspace_bytes,
+                                 const int32_t* rowptr, int32_t* center, int32_t* nbr, int32_t* cell_shift, void* shift_vec, aa_stream stream) {
+  NlFramesDev d{};
+  if (int rc = plan_nl_frames(in, frames, workspace, workspace_bytes, "aa_nl_frames_fill", d)) return rc;
+  AA_REQUIRE(rowptr && center && nbr, "aa_nl_frames_fill: null output");
+  if (d.N == 0 || d.B == 0) return AA_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 waves((unsigned)((d.N + 3) / 4));
+  if (in->dtype == AA_F32)
+    hipLaunchKernelGGL((nlf_pairs_kernel<float, true>), waves, dim3(256), 0, s, d, rowptr, center, nbr, cell_shift, shift_vec);
+  else
+    hipLaunchKernelGGL((nlf_pairs_kernel<double, true>), waves, dim3(256), 0, s, d, rowptr, center, nbr, cell_shift, shift_vec);
+  AA_CHECK_HIP(hipGetLastError());
+  return AA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // aa_graph_prune_*: stable compaction of a center-sorted list somebody else built, by per-type-pair cutoffs.
 // ONE WAVE PER CENTER SEGMENT (four per workgroup), 64 edges per pass: the lanes read nbr / shift_vec of consecutive edges, so
 // these streams are coalesced, which a thread-per-atom loop (the form of nl_pairs_kernel, whose inner loop walks cells, not a

@@ -741,6 +741,84 @@ def neighbor_list(pos: torch.Tensor, cell, pbc, r_cut: float, lib: Optional[_lib
     return DeviceNeighborList(edge_index, rowptr, cell_shift, shift_vec, lib)
 
 
+class Frames:
+    """`aa_frames`: a batch of frames concatenated in atom order.  `frame_atoms` [B+1]: frame b owns the atoms
+    [frame_atoms[b], frame_atoms[b+1]); non-decreasing, within [0, N].  Holds the int32 offsets on their device and `num_frames`;
+    a tensor that is already int32 is kept as it is and never read by the host (the kernels clamp what they are given)."""
+
+    def __init__(self, frame_atoms, device=None):
+        t = torch.as_tensor(frame_atoms)
+        if t.dim() != 1 or t.numel() < 1 or t.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"Frames: frame_atoms must be B + 1 int32 / int64 offsets, not {list(t.shape)} {t.dtype}")
+        self.frame_atoms = t.detach().to(device=device if device is not None else t.device, dtype=torch.int32).contiguous()
+        self.num_frames = int(t.numel()) - 1
+
+    @classmethod
+    def from_batch(cls, batch: torch.Tensor, num_frames: Optional[int] = None) -> "Frames":
+        """From nequip's `batch` vector (the frame of every atom).  Checks once, on the host, that it is non-decreasing (frames
+        contiguous in atom order) and raises ValueError otherwise; frames without atoms are legal."""
+        b = batch.detach().reshape(-1).long()
+        if b.numel() > 1 and bool((b[1:] < b[:-1]).any()):
+            raise ValueError("Frames.from_batch: batch must be non-decreasing (frames contiguous in atom order)")
+        have = int(b[-1]) + 1 if b.numel() else 0
+        if b.numel() and int(b[0]) < 0:
+            raise ValueError("Frames.from_batch: negative frame index")
+        nf = have if num_frames is None else int(num_frames)
+        if nf < have:
+            raise ValueError(f"Frames.from_batch: batch names frame {have - 1}, num_frames is {nf}")
+        counts = torch.bincount(b, minlength=nf)
+        offsets = torch.zeros(nf + 1, dtype=torch.int64, device=b.device)
+        offsets[1:] = torch.cumsum(counts, 0)
+        return cls(offsets)
+
+    def c_struct(self) -> _lib.Frames:
+        return _lib.Frames(self.num_frames, self.frame_atoms.data_ptr())
+
+
+def neighbor_list_frames(pos: torch.Tensor, cells: torch.Tensor, pbc, r_cut: float, frames: Frames,
+                         lib: Optional[_lib.AllegroLib] = None) -> DeviceNeighborList:
+    """The neighbour list of a batch of small frames in one pair of calls (`aa_nl_frames_count` / `aa_nl_frames_fill`): `pos` [N,3]
+    holds the frames one after the other, `cells` [B,3,3] one cell per frame (lattice vectors as rows), `pbc` one setting for all.
+    Same conventions and the same result type as `neighbor_list` -- global atom ids, `shift_vec` from each edge's own cell -- so
+    `.prepare`, `.prune` and `.ghost_layout` apply.  Inside a centre's segment: image ascending, then neighbour id.  Only the edge
+    count and the error flags cross to the host.  All pairs of a frame are tested: for frames of up to a few thousand atoms."""
+    lib = lib if lib is not None else _lib.load()
+    _require_gpu(lib, pos, "neighbor_list_frames")
+    if pos.dtype not in _TORCH2AA or pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError(f"neighbor_list_frames: pos must be [N, 3] float32 / float64, not {list(pos.shape)} {pos.dtype}")
+    pos = pos.detach().contiguous()
+    N, dev, B = pos.shape[0], pos.device, frames.num_frames
+    cells_d = torch.as_tensor(cells).detach().to(device=dev, dtype=torch.float64).reshape(-1, 9).contiguous()
+    if cells_d.shape[0] != B:
+        raise ValueError(f"neighbor_list_frames: {B} frames, {cells_d.shape[0]} cells")
+    if frames.frame_atoms.device != dev:
+        raise ValueError(f"neighbor_list_frames: the frame offsets live on {frames.frame_atoms.device}, the positions on {dev}")
+    inp = _lib.NlFramesInput()
+    inp.num_atoms, inp.pos, inp.cells, inp.dtype, inp.r_cut = N, pos.data_ptr(), cells_d.data_ptr(), _TORCH2AA[pos.dtype], float(r_cut)
+    if isinstance(pbc, bool):
+        pbc = (pbc,) * 3
+    for q in range(3):
+        inp.pbc[q] = int(bool(pbc[q]))
+    fs = frames.c_struct()
+    nbytes = lib.lib.aa_nl_frames_workspace_bytes(N, B)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    n_edges = C.c_int64()
+    stream = _stream_ptr(pos)
+    with _device_ctx(dev):
+        lib.check(lib.lib.aa_nl_frames_count(C.byref(inp), C.byref(fs), ws.data_ptr(), nbytes, rowptr.data_ptr(), C.byref(n_edges), stream),
+                  "aa_nl_frames_count")
+        E = int(n_edges.value)
+        edge_index = torch.empty((2, E), dtype=torch.int32, device=dev)
+        cell_shift = torch.empty((E, 3), dtype=torch.int32, device=dev)
+        shift_vec = torch.empty((E, 3), dtype=pos.dtype, device=dev)
+        if E > 0:
+            lib.check(lib.lib.aa_nl_frames_fill(C.byref(inp), C.byref(fs), ws.data_ptr(), nbytes, rowptr.data_ptr(), edge_index[0].data_ptr(),
+                                                edge_index[1].data_ptr(), cell_shift.data_ptr(), shift_vec.data_ptr(), stream),
+                      "aa_nl_frames_fill")
+    return DeviceNeighborList(edge_index, rowptr, cell_shift, shift_vec, lib)
+
+
 ZBL_QQR2E = {"metal": 14.399645, "real": 332.06371}  # LAMMPS' qqr2e: eV Angstrom / kcal/mol Angstrom per squared elementary charge
 
 
@@ -1342,16 +1420,62 @@ class HipAllegroModel(torch.nn.Module):
                                "(it keeps no frame-wide edge arrays): call energy_forces with forces first")
         return lib, cap
 
-    def _observable(self, step, name: str, graph: PreparedGraph, out: torch.Tensor, *args) -> torch.Tensor:
+    def _observable(self, step, name: str, graph: PreparedGraph, out: torch.Tensor, *args, frames: Optional[Frames] = None) -> torch.Tensor:
         """`aa_model_<name>` into `out`, or `aa_model_blocked_<name>` (the cap behind the graph) when the last step was a blocked one;
-        `step`: what `_after_step` returned."""
+        `step`: what `_after_step` returned.  `frames`: the descriptor of a per-frame sum, which goes in front of the workspace."""
         lib, cap = step
         fn = f"aa_model_{name}" if cap is None else f"aa_model_blocked_{name}"
         g = graph.c_struct()
+        head = () if cap is None else (cap,)
+        if frames is not None:
+            fs = frames.c_struct()
+            head += (C.byref(fs),)
         with _device_ctx(out.device):
-            lib.check(getattr(lib.lib, fn)(self._plan_handle, C.byref(g), *(() if cap is None else (cap,)), self._workspace.data_ptr(),
+            lib.check(getattr(lib.lib, fn)(self._plan_handle, C.byref(g), *head, self._workspace.data_ptr(),
                                            self._workspace.numel(), *args, out.data_ptr(), _stream_ptr(out)), fn)
         return out
+
+    def _frames_on(self, frames: Frames, device, what: str) -> Frames:
+        if not isinstance(frames, Frames):
+            raise ValueError(f"{what}: frames must be a Frames (Frames(frame_atoms) or Frames.from_batch(batch))")
+        if frames.frame_atoms.device != device:
+            raise ValueError(f"{what}: the frame offsets live on {frames.frame_atoms.device}, the step ran on {device}")
+        return frames
+
+    def frame_energies(self, e_atom: torch.Tensor, frames: Frames) -> torch.Tensor:
+        """Per-frame energies [B] of a batch: the sum of `e_atom` [N] over each frame's atoms (`aa_model_frame_energies`), in double in
+        a fixed order, rounded once.  A frame's bits depend on its own atoms only; an empty frame gives +0."""
+        lib, _ = self._after_step("frame_energies")
+        e = e_atom.detach().reshape(-1)
+        if e.dtype != self.dtype:
+            raise ValueError(f"frame_energies: e_atom must be {self.dtype}, not {e.dtype}")
+        e = e.contiguous()
+        frames = self._frames_on(frames, e.device, "frame_energies")
+        out = torch.empty(frames.num_frames, dtype=self.dtype, device=e.device)
+        fs = frames.c_struct()
+        with _device_ctx(e.device):
+            lib.check(lib.lib.aa_model_frame_energies(self._plan_handle, C.byref(fs), e.numel(), e.data_ptr(), out.data_ptr(), _stream_ptr(e)),
+                      "aa_model_frame_energies")
+        return out
+
+    def frame_virial(self, graph: PreparedGraph, frames: Frames) -> torch.Tensor:
+        """`virial` frame by frame [B,3,3] for a batch stepped as one graph (`aa_model_frame_virial`): dE/d(strain) restricted to each
+        frame's edges, same convention; the rows sum to `virial(graph)`.  One workgroup per frame, no atomics: bit-reproducible, and
+        a frame's bits do not depend on the other frames.  A lone large frame belongs on `virial`."""
+        step = self._after_step("frame_virial")
+        frames = self._frames_on(frames, self._workspace.device, "frame_virial")
+        out = torch.empty((frames.num_frames, 3, 3), dtype=self.dtype, device=self._workspace.device)
+        return self._observable(step, "frame_virial", graph, out, frames=frames)
+
+    def frame_heat_flux_potential(self, graph: PreparedGraph, frames: Frames, velocities: torch.Tensor) -> torch.Tensor:
+        """`heat_flux_potential` frame by frame [B,3] (`aa_model_frame_heat_flux`); `velocities` [N,3] of the whole batch."""
+        if tuple(velocities.shape) != (graph.num_atoms, 3):
+            raise ValueError(f"velocities must be [{graph.num_atoms}, 3], not {list(velocities.shape)}")
+        step = self._after_step("frame_heat_flux_potential")
+        frames = self._frames_on(frames, self._workspace.device, "frame_heat_flux_potential")
+        vel = velocities.detach().to(device=self._workspace.device, dtype=self.dtype).contiguous()
+        out = torch.empty((frames.num_frames, 3), dtype=self.dtype, device=self._workspace.device)
+        return self._observable(step, "frame_heat_flux", graph, out, vel.data_ptr(), frames=frames)
 
     def virial(self, graph: PreparedGraph) -> torch.Tensor:
         """dE/d(strain) [3,3] of the LAST `energy_forces(..., with_forces=True)` call on `graph` (stress = virial / volume,
@@ -1445,6 +1569,19 @@ class HipAllegroModel(torch.nn.Module):
         graph.shift_vec = shift_vec
         return graph
 
+    def _frames_for(self, batch: torch.Tensor, num_frames: int) -> Optional[Frames]:
+        """The `Frames` of a `batch` vector, cached like the graph (identity + in-place version of `batch`, kept alive by the entry);
+        None for a batch that is not non-decreasing, which keeps the `index_add_` route."""
+        key = (batch.data_ptr(), int(batch._version), int(batch.numel()), int(num_frames), str(batch.device))
+        cached = getattr(self, "_frames_cache", None)
+        if cached is None or cached[0] != key:
+            try:
+                frames = Frames.from_batch(batch, num_frames)
+            except ValueError:
+                frames = None
+            self._frames_cache = cached = (key, batch, frames)
+        return cached[2]
+
     def forward(self, data: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """AtomicDataDict in, AtomicDataDict out (keys: pos, edge_index, atom_types [, cell, edge_cell_shift, batch])."""
         pos = data["pos"]
@@ -1455,8 +1592,13 @@ class HipAllegroModel(torch.nn.Module):
         out = dict(data)
         out["atomic_energy"] = e_atom.unsqueeze(-1)
         nf = 1
+        frames = None
         if "batch" in data:
             nf = int(data["cell"].reshape(-1, 3, 3).shape[0]) if "cell" in data else int(data["batch"].max()) + 1
+            frames = self._frames_for(data["batch"], nf)
+        if frames is not None:  # frames contiguous in atom order: one fixed-order kernel per observable
+            out["total_energy"] = self.frame_energies(e_atom, frames).unsqueeze(-1)
+        elif "batch" in data:
             out["total_energy"] = torch.zeros(nf, 1, dtype=self.dtype, device=pos.device).index_add_(0, data["batch"], e_atom.unsqueeze(-1))
         else:
             out["total_energy"] = e_atom.sum().reshape(1, 1)
@@ -1466,6 +1608,8 @@ class HipAllegroModel(torch.nn.Module):
             cell = data["cell"].to(self.dtype).reshape(-1, 3, 3)
             if nf == 1:
                 w = self.virial(graph).unsqueeze(0)
+            elif frames is not None:
+                w = self.frame_virial(graph, frames)
             else:
                 # per-frame strain derivative from the per-edge dE/dr_e and r_e the step left in the workspace
                 d = self.debug_tap("dvec", graph, with_forces=True)[:, :3]

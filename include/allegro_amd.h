@@ -380,7 +380,8 @@ int aa_model_energy_forces(const aa_model_plan* plan, const void* dev_weights, c
 int aa_model_plan_describe(const aa_model_plan* plan, char* buf, size_t buf_bytes);
 
 /* Synchronises `stream` and reports whether any step enqueued on this plan since the last report contradicted the graph
- * hints it was given (aa_graph.max_degree too small, center atoms with edges outside [atom_begin, atom_end)):
+ * hints it was given (aa_graph.max_degree too small, center atoms with edges outside [atom_begin, atom_end)), was cut at a wrong
+ * edge (section 2b) or was handed frame offsets that had to be clamped (section 2c):
  * AA_ERR_INVALID + aa_last_error() then, AA_OK otherwise; the condition is cleared.  aa_model_energy_forces performs the
  * same test (without synchronising) on entry, so a host that never calls this still gets the error one step late. */
 int aa_model_check(const aa_model_plan* plan, aa_stream stream);
@@ -478,6 +479,47 @@ int aa_model_blocked_atom_virial(const aa_model_plan* plan, const aa_graph* grap
 int aa_model_blocked_heat_flux(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges, void* workspace,
                                size_t workspace_bytes, const void* velocities, void* flux3, aa_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 2c. Batches of frames: many small structures concatenated into ONE graph, stepped by ONE aa_model_energy_forces call (the
+ *    step is batch-agnostic: a batch is a larger center-sorted graph), then read off frame by frame.
+ *
+ *    Frames are contiguous in atom order; the graph is center-sorted, so frame b's edges are the contiguous range
+ *    [rowptr[frame_atoms[b]], rowptr[frame_atoms[b + 1]]).  The ranges need not cover all atoms.
+ *    CONTRACT, not checked: every edge's neighbour lies in its centre's frame (what aa_nl_frames_* and any per-structure list give).
+ *
+ *    The offsets live on the device, so the host cannot validate them without a synchronisation; the kernels clamp instead:
+ *    lo = clamp(frame_atoms[b], 0, N), hi = clamp(frame_atoms[b + 1], lo, N), and nothing ever indexes outside the frame's arrays.
+ *    Where the clamp changed a value the kernel writes NaN into that frame's output row and raises the plan's status word (the
+ *    mechanism of the graph hints and the block cuts): the next aa_model_energy_forces* on the plan, or aa_model_check, returns
+ *    AA_ERR_INVALID naming the frame (one of them, where several were wrong).
+ *
+ *    aa_model_frame_energies   out_b [B]:    the sum of atom_energy [num_atoms] over each frame's atoms.  Needs no step and no workspace.
+ *    aa_model_frame_virial     out_b9 [B,9]: the W of aa_model_virial restricted to each frame's edges, same index convention.
+ *    aa_model_frame_heat_flux  out_b3 [B,3]: the J_pot of aa_model_heat_flux restricted to each frame's edges (velocities [num_atoms,3]).
+ *    aa_model_blocked_frame_virial / aa_model_blocked_frame_heat_flux: the same after aa_model_energy_forces_blocked, found through
+ *    max_block_edges as the other blocked twins are.
+ *    The last four read what the LAST step with forces left in `workspace` (the checks of aa_model_virial / aa_model_heat_flux).
+ *    Outputs are device memory in the model dtype.  One launch each: one 256-lane workgroup per frame sums its rows in double in a
+ *    fixed order and rounds once; no atomics, no scratch (aa_model_workspace_bytes is unchanged).  A frame's bits depend on that
+ *    frame's rows only -- not on B, the other frames or the call.  An empty frame gives +0; B = 0 launches nothing and returns AA_OK.
+ *    LIMIT: the parallelism is B workgroups.  A lone large frame belongs on aa_model_virial / aa_model_heat_flux, which spread one
+ *    frame over the device.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct aa_frames {
+  int32_t num_frames;          /* B >= 0 */
+  const int32_t* frame_atoms;  /* DEVICE [B+1]: atoms [frame_atoms[b], frame_atoms[b+1]) are frame b; non-decreasing, within [0, N] */
+} aa_frames;
+int aa_model_frame_energies(const aa_model_plan* plan, const aa_frames* frames, int64_t num_atoms, const void* atom_energy, void* out_b,
+                            aa_stream stream);
+int aa_model_frame_virial(const aa_model_plan* plan, const aa_graph* graph, const aa_frames* frames, void* workspace, size_t workspace_bytes,
+                          void* out_b9, aa_stream stream);
+int aa_model_frame_heat_flux(const aa_model_plan* plan, const aa_graph* graph, const aa_frames* frames, void* workspace,
+                             size_t workspace_bytes, const void* velocities, void* out_b3, aa_stream stream);
+int aa_model_blocked_frame_virial(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges, const aa_frames* frames,
+                                  void* workspace, size_t workspace_bytes, void* out_b9, aa_stream stream);
+int aa_model_blocked_frame_heat_flux(const aa_model_plan* plan, const aa_graph* graph, int64_t max_block_edges, const aa_frames* frames,
+                                     void* workspace, size_t workspace_bytes, const void* velocities, void* out_b3, aa_stream stream);
+
 /* debug/parity taps: copy an intermediate of the LAST call out of the workspace layout.
  * name in {"edge_attrs","edge_embedding","edge_features","emb0","vec"}; a "+f" suffix selects the workspace layout of
  * a step that computed forces (required for "dvec": dE/dr_e [E,4]); returns elements per edge or <0 */
@@ -530,6 +572,35 @@ int aa_nl_count_typed(const aa_nl_input* in, const aa_nl_types* types, void* wor
                       int64_t* num_edges, aa_stream stream);
 int aa_nl_fill_typed(const aa_nl_input* in, const aa_nl_types* types, void* workspace, size_t workspace_bytes,
                      const int32_t* rowptr, int32_t* center, int32_t* nbr, int32_t* cell_shift, void* shift_vec, aa_stream stream);
+
+/* The list of a BATCH of frames (aa_frames, section 2c) in one pair of calls: every frame has its own cell, all share pbc and r_cut.
+ * Conventions and outputs are those of aa_nl_count / aa_nl_fill for the whole batch -- rowptr [N+1], center / nbr [E] (GLOBAL atom
+ * ids), cell_shift [E,3], shift_vec [E,3] in the position dtype, computed from each edge's OWN frame cell; geometry in double; atoms
+ * wrapped into their cell along periodic directions and the wrap undone in cell_shift -- and every neighbour lies in its centre's
+ * frame, the contract of section 2c.  Atoms that belong to no frame get no edges.
+ * Frames are small, so there is no cell grid: a set-up kernel (one thread per frame: inverse cell, perpendicular heights h, image
+ * counts k[a] = pbc[a] ? ceil(r_cut / h[a]) : 0), then one wave per centre atom tests every atom of its frame in every image.  The work
+ * is O(n_f^2 * images) per frame: this is for frames of up to a few thousand atoms; larger frames go to aa_nl_*.
+ * ORDER inside a centre's segment, stable and free of atomics: image (n0, n1, n2) of the wrapped positions ascending (n0 slowest),
+ * then neighbour id ascending; for atoms that lie inside their cell cell_shift IS (n0, n1, n2).
+ *   aa_nl_frames_count  writes rowptr and returns E; makes the one synchronisation, which also brings the error flags back:
+ *                       AA_ERR_INVALID naming the first frame with a singular cell, with more than 64 images along a direction, or
+ *                       with offsets outside [0, N] / decreasing (they are clamped: nothing is read out of bounds).
+ *   aa_nl_frames_fill   same input, same workspace; after a count that failed it writes nothing.
+ * `workspace`: aa_nl_frames_workspace_bytes(num_atoms, num_frames) bytes of device scratch. */
+typedef struct {
+  int64_t num_atoms;
+  const void* pos;         /* [N,3] device, `dtype`                                            */
+  const double* cells;     /* DEVICE [B,9] doubles: per frame, lattice vectors as rows          */
+  int32_t pbc[3];          /* periodic along a, b, c -- one setting for all frames             */
+  int32_t dtype;           /* aa_dtype of pos / shift_vec                                      */
+  double r_cut;
+} aa_nl_frames_input;
+size_t aa_nl_frames_workspace_bytes(int64_t num_atoms, int32_t num_frames);
+int aa_nl_frames_count(const aa_nl_frames_input* in, const aa_frames* frames, void* workspace, size_t workspace_bytes, int32_t* rowptr,
+                       int64_t* num_edges, aa_stream stream);
+int aa_nl_frames_fill(const aa_nl_frames_input* in, const aa_frames* frames, void* workspace, size_t workspace_bytes,
+                      const int32_t* rowptr, int32_t* center, int32_t* nbr, int32_t* cell_shift, void* shift_vec, aa_stream stream);
 
 /* The same reduction for a center-sorted list somebody else built at the largest cutoff (a LAMMPS list, an untyped aa_nl list):
  * stable compaction, keeping edge e iff |pos[nbr_e] - pos[center_e] + shift_vec_e| < cutoffs[type_center][type_nbr] (evaluated in
