@@ -205,8 +205,10 @@ class HaloShard:
             self._install_plan(send_counts, ids_out)
         else:
             self._install_plan([0] * world, torch.empty(0, dtype=torch.int64, device=device))
+        # (a rank without atoms: the graph is a record of sizes only -- no library call for it, and no step ever runs on it: `_local_step`)
         self.graph = PreparedGraph(edge_index_local.to(device), torch.as_tensor(types_local).to(device), self.n_own + self.n_ghost,
-                                   None if shift_vec is None else shift_vec.to(device=device, dtype=dtype))
+                                   None if shift_vec is None else shift_vec.to(device=device, dtype=dtype),
+                                   transposed=self.n_own + self.n_ghost > 0)
         self._bufs = None
 
     def _install_plan(self, send_counts, send_gids: torch.Tensor):
@@ -300,7 +302,11 @@ class HaloShard:
         (device, model dtype) and `types_all` are needed in full (as an MD code has them at start-up), and the slab sort
         (`frac`, `argsort`, `rank_of`, `lookup`: a few 8-byte words per atom) runs over all N atoms on every rank -- 97 336
         atoms at C4, i.e. ~5 MB of transient arrays; a domain-decomposed host hands over its slab instead: `from_owned`.  Full periodic
-        `cell` (3x3, rows).  Results come back in SLAB order: `shard.owned_ids()` maps them to the caller's numbering."""
+        `cell` (3x3, rows).  Results come back in SLAB order: `shard.owned_ids()` maps them to the caller's numbering.
+        With more ranks than atoms some blocks are empty.  Such a rank gets a shard of zero atoms: no halo (a slab without atoms has
+        no extent, so nothing is a candidate), no edges, `local_gids` and `owned_ids()` empty.  It still takes part in the plan
+        exchange and in every collective of the step, so the other ranks never wait for it, and `energy_forces_halo` returns
+        `E_i` [0] and forces [0, 3] on it (`virial` / `heat_flux`: the frame's values, as on every rank)."""
         from .nn import neighbor_list
 
         dev, dtype = pos_all.device, pos_all.dtype
@@ -312,6 +318,10 @@ class HaloShard:
         cuts = [(N * r) // world for r in range(world + 1)]
         a0, a1 = cuts[rank], cuts[rank + 1]
         own = order[a0:a1]
+        if a1 == a0:  # an empty block: nothing to list, nothing to ask of the others (the plan exchange in `__init__` still takes place)
+            none = torch.empty(0, dtype=torch.int64, device=dev)
+            return cls(rank, world, cuts, none.cpu(), torch.empty((2, 0), dtype=torch.int64, device=dev), none,
+                       torch.empty((0, 3), dtype=dtype, device=dev), dev, dtype, order=order, group=group, connect=connect)
         # halo candidates: within r_cut of the slab along the axis (periodic); the slab's extent from its own atoms
         height = float(torch.linalg.det(cell_t).abs() / torch.linalg.norm(torch.linalg.cross(cell_t[(axis + 1) % 3], cell_t[(axis + 2) % 3])))
         margin = 1.02 * float(r_cut) / height
@@ -472,11 +482,23 @@ def _check_observables(atom_virial):
         raise ValueError(f"atom_virial must be None or one of {list(_ATTRIBUTIONS)}, not {atom_virial!r}")
 
 
+def _local_step(model, shard: HaloShard, pos_loc: torch.Tensor):
+    """The hot path on one shard's local arrays: (E_i [n_own + n_ghost], forces [n_own + n_ghost, 3]).  A shard without atoms
+    (more ranks than atoms, a slab over vacuum) runs no kernel -- the library takes no null arrays -- and returns empty rows."""
+    if shard.n_own + shard.n_ghost == 0:
+        return pos_loc.new_zeros(0), pos_loc.new_zeros((0, 3))
+    return model.energy_forces(pos_loc, shard.graph)
+
+
 def _shard_observables(model, shard: HaloShard, virial: bool, atom_virial, vel_loc):
     """What one shard contributes, read off the step that has JUST run on `shard.graph` (the model's workspace still holds it):
     (sums, w).  `sums`: float64 [9 if virial] + [3 if vel_loc is given], this shard's part of dE/d(strain) and of the potential
     heat flux -- a shard's edges are those of its owned centers, so the parts add up over the ranks; None when neither is asked for.
     `w`: the local per-atom virial [n_own + n_ghost, 9] (owned rows first) or None."""
+    if shard.n_own + shard.n_ghost == 0:  # no step ran on a shard without atoms (`_local_step`): it contributes zeros
+        dev, n = shard.local_gids.device, (9 if virial else 0) + (3 if vel_loc is not None else 0)
+        return (torch.zeros(n, dtype=torch.float64, device=dev) if n else None,
+                torch.zeros((0, 9), dtype=model.dtype, device=dev) if atom_virial is not None else None)
     parts = []
     if virial:
         parts.append(model.virial(shard.graph).reshape(9).double())
@@ -526,7 +548,7 @@ def energy_forces_halo(model, pos_own: torch.Tensor, shard: HaloShard, *, virial
         vel_loc, send_v = shard.pack_velocities(velocities_own)
         if multi:
             _all_to_all_rows(vel_loc[n_own:], send_v, shard.recv_counts, shard.send_counts, shard.group, shard.host_staged)
-    e_loc, f_loc = model.energy_forces(pos_loc, shard.graph)
+    e_loc, f_loc = _local_step(model, shard, pos_loc)
     f_own = f_loc[:n_own]
     if multi:
         ns = recv_r.shape[0] - 1
@@ -625,7 +647,7 @@ class InProcessHaloGroup:
             vels = [vp[0] for vp in vpk]
         res, local = [], []
         for s, pk, vel_loc in zip(self.shards, packed, vels):
-            e_loc, f_loc = model.energy_forces(pk[0], s.graph)
+            e_loc, f_loc = _local_step(model, s, pk[0])
             res.append((e_loc.clone(), f_loc.clone()))  # (the model's output buffers are reused by the next shard's step)
             if want_obs:  # (and so is its workspace: this shard's observables are read before the next shard's step)
                 local.append(_shard_observables(model, s, virial, atom_virial, vel_loc))
