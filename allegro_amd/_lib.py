@@ -41,7 +41,7 @@ class PlanOptions(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "tp_generic", "tp_no_chain", "tp_no_moments", "tp_no_operator", "tp_force_operator", "tp_operator_fused",
         "gemm_no_chain", "gemm_fp32_mfma", "gemm_valu", "gemm_v1", "gemm_lds_epilogue", "f64_column_loop",
-        "embed_no_fuse", "fused_forward", "moments_waves_per_block", "f64_rows", "no_channel_padding", "poison_workspace", "no_slot_form", "op_proj_gemm", "op_env_vector", "staged_no_fold", "op_recompute_bvecs", "readout_two_pass", "tp_prefer_moments", "fused_narrow", "chain_staged_weights")]
+        "embed_no_fuse", "fused_forward", "moments_waves_per_block", "f64_rows", "no_channel_padding", "poison_workspace", "no_slot_form", "op_proj_gemm", "op_env_vector", "staged_no_fold", "op_recompute_bvecs", "readout_two_pass", "tp_prefer_moments", "fused_narrow", "chain_staged_weights", "mom0_epilogue")]
 
 
 def options_from_env() -> PlanOptions:
@@ -69,6 +69,7 @@ def options_from_env() -> PlanOptions:
     o.tp_prefer_moments = flag("AA_TP_PREFER_MOM")  # A/B: the round-4 selection (moments kernels) where the operator kernels are now preferred
     o.fused_narrow = {"1": 1, "2": 2, "3": 3, "4": 4}.get(env.get("AA_FUSED_NARROW", "")[:1], 0)  # A/B: 1 = the one-wave-per-SIMD fused forward, 2 = the eight-wave form (+ deep tail) at any size, 3 = the four-wave form at any size, 4 = the eight-wave form with the chain-only tail at any size
     o.chain_staged_weights = flag("AA_CHAIN_STAGED")  # A/B: the general chain kernel for the one-layer reverse chains
+    o.mom0_epilogue = {"1": 1, "0": 2}.get(env.get("AA_MOM0_EPILOGUE", "")[:1], 0)  # A/B: per-edge half of the layer-0 moments reverse in the last chain's epilogue: 1 wherever it applies, 0 never
     o.poison_workspace = flag("AA_POISON")  # debugging: NaN-filled workspace before every step
     o.f64_rows = {"0": 2, "2": 1}.get(env.get("AA_F64_ROWS", "")[:1], 0)  # 0: off, 2: wherever applicable
     return o

@@ -292,6 +292,15 @@ struct ChainLayer {
                        // readout layer folded into the epilogue, so the edge sum reads 4 B/edge instead of a row
   void* kept_out;      // [M, ld_kept] or nullptr: the kept 64 features AS KEPT (activated if keep_act) are also stored -- the hidden
   int ld_kept;         // activation a later launch consumes where the folded-away output layer's result used to be (staged forward)
+  // Moments epilogue of the 64-wide layer of a ONE-layer chain that stores no tile (the per-edge half of the layer-0 moments reverse; rows
+  // center-sorted, ChainArgs::center set): with GM = mom_gm0[center(e)] and h = mom_h[e],
+  //   C[e,k] <- (C[e,k] + sum_j mom_y[e,j] GM[j][k]) silu'(h[e,k])     and     mom_dy[e,j] = sum_k silu(h[e,k]) GM[j][k]
+  // (the layer itself carries no z / add operands)
+  const void* mom_gm0;  // [atoms][mom_d][64] or nullptr
+  const void* mom_y;    // [M, ld_mom_y] harmonics
+  const void* mom_h;    // [M, ld_mom_h] pre-activations
+  void* mom_dy;         // [M, ld_mom_dy]
+  int mom_d, ld_mom_y, ld_mom_h, ld_mom_dy;  // mom_d: 4 or 9
 };
 struct ChainArgs {
   int64_t M;
@@ -540,6 +549,7 @@ struct TpMomArgs {
   int ld_ga;
   int ka_lds;           // row stride of the wave-private moment patch in LDS (set by the launcher: max(ka0, ka1))
   int waves_per_block;  // 0 = 1 (aa_plan_options.moments_waves_per_block)
+  void* gm0;            // launch_tp_mom_bwd_first_gm: [N][D][64] per-atom GM0 (g_a and the layer-0 slab of gsh_env stay unwritten)
 };
 // Per-atom operator form of the tensor-product track for L <= 3 layers, u = 64*m (aa_tp_op.hip)
 struct TpOpArgs {
@@ -600,6 +610,7 @@ template <typename T>
 int launch_tp_mom_bwd_last(int pair, const TpMomArgs& a, hipStream_t stream);
 template <typename T>
 int launch_tp_mom_bwd_first(int pair, const TpMomArgs& a, hipStream_t stream);
+int launch_tp_mom_bwd_first_gm(int pair, const TpMomArgs& a, hipStream_t stream);  // fp32: stops after GM0 (TpMomArgs::gm0)
 template <typename T>
 int launch_tp_chain_fwd_last(int pair, const TpChainArgs& a, hipStream_t stream);
 template <typename T>

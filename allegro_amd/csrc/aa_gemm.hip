@@ -1176,6 +1176,9 @@ struct ChainLayerDev {
   int ld_kept, pad3_;
   const float *a2_add, *a2_z;  // a_mode 2 operand transform
   int ld_a2add, ld_a2z;
+  const float *mom_gm0, *mom_y, *mom_h;  // moments epilogue (ChainLayer::mom_gm0)
+  float* mom_dy;
+  int ld_mom_y, ld_mom_h, ld_mom_dy, pad4_;
   const float* a[kChainMaxBlocks];
   int lda[kChainMaxBlocks];
   ChainTileDev t[kChainMaxBlocks];
@@ -1202,13 +1205,19 @@ struct ChainDev {
 // conflict-free ds_read_b128.  Operand rows are loaded one step ahead, also across tile-pair and layer
 // boundaries; rows beyond M are clamped for loads and masked for stores.
 constexpr int kEpLd = 36;          // row stride (floats) of the store-transpose patch: 32 + 4 keeps b128 accesses conflict-light
+// Moments epilogue: GM0 blocks ([D][64] floats per atom, D <= 9) a workgroup stages.  A chain with this epilogue stores no tile, so the
+// blocks lie where the four store-transpose patches would be: 4 x 32 x kEpLd = 4608 floats = 8 blocks of 9 x 64 -- no LDS is added
+// and the three workgroups per CU stay.  128 center-sorted rows at 28 edges per atom span at most 6 atoms.
+constexpr int kChainMomSlots = 8;
+static_assert(kChainMomSlots * 9 * 64 <= 4 * 32 * kEpLd, "the GM0 blocks alias the store-transpose patches");
 
 // PRE: layers with at most two k chunks and more than two output tiles (a chained 64-wide operand feeding a wide
 // layer) split their operand once and reuse it for every tile pair; that costs 48 VGPRs, so the variant without
 // such layers runs at 3 waves/SIMD and the one with them at 2.
 // EMB: the embrev_out epilogue (reverse of the two-body basis expansion) is compiled in; only the last reverse chain
 // of a step uses it, and it costs registers the other chains should not pay for.
-template <bool PRE, bool EMB>
+// MOMD: the moments epilogue of the last layer (ChainLayer::mom_gm0) at D = MOMD spherical-harmonic components is compiled in; 0: none.
+template <bool PRE, bool EMB, int MOMD = 0>
 __global__ __launch_bounds__(256, PRE ? 2 : 3) void gemm_chain_bf16x3_kernel(ChainDev c) {
   // (which split: see split3_pack_masked)
   auto chain_split = [](const v4f* a, u32x4* l1, u32x4* l2, u32x4* l3) {
@@ -1241,6 +1250,24 @@ __global__ __launch_bounds__(256, PRE ? 2 : 3) void gemm_chain_bf16x3_kernel(Cha
     float* tab = const_cast<float*>(sTab);
     for (int i = tid; i < c.num_types * c.num_types * 512; i += 256) tab[i] = c.emb_table[i];
     sTab += (c.types[c.center[gmc]] * c.num_types + c.types[c.nbr[gmc]]) * 512;
+  }
+  // moments epilogue: the rows are center-sorted, so the centers of this workgroup's 128 rows are one contiguous atom range; where it
+  // fits the slots its GM0 blocks are staged (visible behind the barrier in front of the first step), otherwise -- low-degree atoms,
+  // general graphs -- every row reads its block from global memory.  The branch is uniform per workgroup.
+  float* sGm = sRo + 32 * kChainMaxBlocks;  // [kChainMomSlots][MOMD][64], in place of the store-transpose patches
+  int mom_c0 = 0;
+  bool mom_lds = false;
+  if constexpr (MOMD > 0) {
+    const ChainLayerDev& ML = c.L[c.nlayers - 1];
+    const int64_t b0 = int64_t(blockIdx.x) * 128, b1 = b0 + 127 < c.M ? b0 + 127 : c.M - 1;
+    mom_c0 = __builtin_amdgcn_readfirstlane(c.center[b0]);
+    const int c1 = __builtin_amdgcn_readfirstlane(c.center[b1]);
+    mom_lds = c1 >= mom_c0 && c1 - mom_c0 < kChainMomSlots;
+    if (mom_lds) {
+      const v4f* src = reinterpret_cast<const v4f*>(ML.mom_gm0 + int64_t(mom_c0) * (MOMD * 64));
+      const int n4 = (c1 - mom_c0 + 1) * (MOMD * 16);
+      for (int i = tid; i < n4; i += 256) reinterpret_cast<v4f*>(sGm)[i] = src[i];
+    }
   }
   // block-cooperative staging: thread t moves elements t, t+256, t+512 of the 768-element step
   auto stage_load = [&](const ChainLayerDev& L, int nt, int kc, u32x4* r) {
@@ -1396,6 +1423,86 @@ __global__ __launch_bounds__(256, PRE ? 2 : 3) void gemm_chain_bf16x3_kernel(Cha
         if (m0 + pr + 8 * q < c.M) *reinterpret_cast<v4f*>(p + int64_t(8 * q) * d.ldc) = v[q];
     }
   };
+  // Moments epilogue of the tile pair of a 64-wide layer, in accumulator layout (register 4 q + i of tile t: feature 32 t + 8 q + 4 hh + i
+  // of this lane's row), with GM = GM0 of the row's center atom, Y the row's harmonics and h the pre-activation the forward stored:
+  //   acc <- (acc + sum_j Y[j] GM[j][k]) silu'(h[k])           (d a_e of the moments, added where g_aenv used to be)
+  //   dY[j] = sum_k silu(h[k]) GM[j][k]                        (layer-0 slab of d Y: in-lane, then across the two lane halves)
+  // Anchors and scheduling barriers per feature group as in tile_scal_accumulate8 (aa_fused8.hip): without them the accumulation
+  // chains of all eight groups are interleaved and spill.
+  auto mom_epilogue = [&](const ChainLayerDev& L, v16f& acc0, v16f& acc1) {
+    constexpr int D = MOMD > 0 ? MOMD : 1;
+    // (row and lane half RE-derived from an opaque copy of the lane: as invariants of the step loop the addresses below are hoisted
+    //  above it, where the kernel has no register to spare, and spilled)
+    unsigned ln = unsigned(lane);
+    opaque_vector(ln);
+    const int hh = int(ln >> 5);
+    const int64_t gm = m0 + int64_t(ln & 31u);
+    const bool row_ok = gm < c.M;
+    const int64_t gmc = row_ok ? gm : c.M - 1;
+    v4f za[4], zb[4];
+    {
+      const float* pz = L.mom_h + gmc * L.ld_mom_h + 4 * hh;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        za[q] = *reinterpret_cast<const v4f*>(pz + 8 * q);
+        zb[q] = *reinterpret_cast<const v4f*>(pz + 32 + 8 * q);
+      }
+    }
+    float Yv[D], gy[D];
+    {
+      const float* py = L.mom_y + gmc * L.ld_mom_y;
+#pragma unroll
+      for (int a = 0; a < D; ++a) {
+        Yv[a] = py[a];
+        gy[a] = 0.f;
+      }
+    }
+    const int ca = c.center[gmc];
+    auto body = [&](const float* bb) {
+#pragma unroll
+      for (int g = 0; g < 8; ++g) {
+        const int q = g & 3;
+        v4f T4 = {0.f, 0.f, 0.f, 0.f}, av;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) av[i] = silu(g < 4 ? za[q][i] : zb[q][i]);
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+          const v4f b = *reinterpret_cast<const v4f*>(bb + a * 64 + 32 * (g >> 2) + 8 * q);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            T4[i] += Yv[a] * b[i];
+            gy[a] += av[i] * b[i];
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          if (g < 4)
+            acc0[4 * q + i] = (acc0[4 * q + i] + T4[i]) * dsilu(za[q][i]);
+          else
+            acc1[4 * q + i] = (acc1[4 * q + i] + T4[i]) * dsilu(zb[q][i]);
+        }
+        if (g < 4)
+          anchor(acc0);
+        else
+          anchor(acc1);
+#pragma unroll
+        for (int a = 0; a < D; ++a) anchor(gy[a]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+    // (ONE copy of the body on a generic pointer -- flat loads, which reach LDS and global memory alike: with a copy per address space
+    //  what the copies have in common is hoisted above the branch, the accumulators are duplicated at the merge, and the kernel spills)
+    const float* gmb = L.mom_gm0 + int64_t(ca) * (D * 64);
+    if (mom_lds) gmb = sGm + (ca - mom_c0) * (D * 64);
+    body(gmb + 4 * hh);
+#pragma unroll
+    for (int a = 0; a < D; ++a) gy[a] += __shfl_xor(gy[a], 32);
+    if (row_ok && hh == 0) {
+      float* gb = L.mom_dy + gm * L.ld_mom_dy;
+#pragma unroll
+      for (int a = 0; a < D; ++a) gb[a] = gy[a];
+    }
+  };
 
   // Every step issues the same vector-memory sequence -- 3 weight-staging loads, then 4 operand-row loads -- on
   // every control path (targets are chosen with scalar selects; a step with nothing to prefetch re-reads layer
@@ -1469,7 +1576,7 @@ __global__ __launch_bounds__(256, PRE ? 2 : 3) void gemm_chain_bf16x3_kernel(Cha
         // this step's operand, split into its three bf16 levels: the prefetched rows or the chained accumulators
         u32x4 x1[2], x2[2], x3[2];
         if (!pre) {
-          if (kc >= KCg) {
+          if (MOMD == 0 && kc >= KCg) {  // (a chain with the moments epilogue is ONE layer: nothing is kept, the 32 registers are the epilogue's)
             v4f a[4];
             kept_a(L, kc - KCg, a);
             chain_split(a, x1, x2, x3);
@@ -1514,8 +1621,13 @@ __global__ __launch_bounds__(256, PRE ? 2 : 3) void gemm_chain_bf16x3_kernel(Cha
 #endif
         ++step;
       }
-      epilogue(L.t[nt], acc0);
-      if (two) epilogue(L.t[nt + 1], acc1);
+      if constexpr (MOMD > 0) {
+        if (L.mom_gm0) mom_epilogue(L, acc0, acc1);  // (64-wide layer: this is its only tile pair)
+      }
+      if constexpr (MOMD == 0) {  // (a chain with the moments epilogue stores no tile and has no z / add operands: launch_gemm_chain checks)
+        epilogue(L.t[nt], acc0);
+        if (two) epilogue(L.t[nt + 1], acc1);
+      }
       if (EMB && L.embrev_out) {  // (64-wide layer: this is its only tile pair)
         float part[8];
 #pragma unroll
@@ -1535,12 +1647,19 @@ __global__ __launch_bounds__(256, PRE ? 2 : 3) void gemm_chain_bf16x3_kernel(Cha
         for (int n = 0; n < 8; ++n) other[n] = part[n];
         permlane32_swap4(part, other);
         permlane32_swap4(part + 4, other + 4);
+        int64_t gms = gm;
+        if constexpr (MOMD > 0) {  // (re-derived: kept across the step loop and the moments epilogue the row index is spilled)
+          unsigned l2 = unsigned(lane);
+          opaque_vector(l2);
+          gms = m0 + int64_t(l2 & 31u);
+        }
         if (row_ok) {  // each lane half stores four of the eight sums of its row
           const int o4 = 4 * hh;
-          *reinterpret_cast<v4f*>(L.embrev_out + gm * 8 + o4) =
+          *reinterpret_cast<v4f*>(L.embrev_out + gms * 8 + o4) =
               v4f{part[o4] + other[o4], part[o4 + 1] + other[o4 + 1], part[o4 + 2] + other[o4 + 2], part[o4 + 3] + other[o4 + 3]};
         }
       }
+      if constexpr (MOMD > 0) return;  // (one layer, one tile pair: nothing of the step loop's state is live in the epilogues above)
       if (L.edge_sum_out) {  // (64-wide layer: this is its only tile pair)
         float part = 0.f;
 #pragma unroll
@@ -1554,7 +1673,7 @@ __global__ __launch_bounds__(256, PRE ? 2 : 3) void gemm_chain_bf16x3_kernel(Cha
         permlane32_swap(t, o);  // both lane halves of a row: own + partner
         if (row_ok && hh == 0) L.edge_sum_out[gm] = t + o;
       }
-      if (nt == L.keep_tile) {  // (the kept pair is the last pair of its layer: nothing reads the old kept tiles any more)
+      if (MOMD == 0 && nt == L.keep_tile) {  // (the kept pair is the last pair of its layer: nothing reads the old kept tiles any more)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           kept0[r] = L.keep_act ? silu(acc0[r]) : acc0[r];
@@ -1590,6 +1709,7 @@ int launch_gemm_chain(const ChainArgs& c, hipStream_t stream) {
     return fail(AA_ERR_INVALID, "gemm chain: the embedding table needs 1..2 types and the edge / type arrays");
   if (c.nlayers < 1 || c.nlayers > 4) return fail(AA_ERR_INVALID, "gemm chain: 1..4 layers");
   bool have_kept = false;
+  int mom_d = 0;
   static_assert(sizeof(ChainDev) <= 4096, "kernel argument block too large");
   for (int li = 0; li < c.nlayers; ++li) {
     const ChainLayer& L = c.L[li];
@@ -1665,6 +1785,20 @@ int launch_gemm_chain(const ChainArgs& c, hipStream_t stream) {
       return fail(AA_ERR_INVALID, "gemm chain: kept_out needs a kept tile pair and 16-B aligned rows");
     D.embrev_out = static_cast<float*>(L.embrev_out);
     if (L.embrev_out && (!c.emb_table || g.N != 64)) return fail(AA_ERR_INVALID, "gemm chain: embrev_out needs the table and a 64-wide layer");
+    if (L.mom_gm0) {
+      auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+      if (c.nlayers != 1 || L.use_prev || L.kept_out || g.N != 64 || g.has_z || g.has_add || (L.mom_d != 4 && L.mom_d != 9) || !L.mom_y || !L.mom_h || !L.mom_dy ||
+          !c.center || !al16(L.mom_gm0) || !al16(L.mom_h) || (L.ld_mom_h & 3) || L.ld_mom_y < L.mom_d || L.ld_mom_dy < L.mom_d)
+        return fail(AA_ERR_INVALID, "gemm chain: the moments epilogue needs a chain of one 64-wide layer without z / add operands, D = 4 or 9 and its arrays");
+      D.mom_gm0 = static_cast<const float*>(L.mom_gm0);
+      D.mom_y = static_cast<const float*>(L.mom_y);
+      D.mom_h = static_cast<const float*>(L.mom_h);
+      D.mom_dy = static_cast<float*>(L.mom_dy);
+      D.ld_mom_y = L.ld_mom_y;
+      D.ld_mom_h = L.ld_mom_h;
+      D.ld_mom_dy = L.ld_mom_dy;
+      mom_d = L.mom_d;
+    }
     D.edge_sum_out = static_cast<float*>(L.edge_sum_out);
     if (L.edge_sum_out) {
       if (!c.ro_w || g.N != 64) return fail(AA_ERR_INVALID, "gemm chain: edge_sum_out needs ro_w and a 64-wide layer");
@@ -1679,7 +1813,17 @@ int launch_gemm_chain(const ChainArgs& c, hipStream_t stream) {
   bool emb = false;
   for (int li = 0; li < d.nlayers; ++li) emb = emb || d.L[li].embrev_out != nullptr;
 #define AA_CHAIN_LAUNCH(P_, E_) hipLaunchKernelGGL((gemm_chain_bf16x3_kernel<P_, E_>), grid, dim3(256), smem, stream, d)
-  if (any_pre) {
+  if (mom_d) {
+    // (its GM0 blocks lie where the store-transpose patches would be: no tile of the chain may be stored)
+    bool stores = false;
+    for (int li = 0; li < d.nlayers; ++li)
+      for (int t = 0; t < d.L[li].NT; ++t) stores = stores || d.L[li].t[t].c != nullptr;
+    if (stores || any_pre || !emb) return fail(AA_ERR_INVALID, "gemm chain: the moments epilogue needs a chain that stores no tile and contracts the embedding");
+    if (mom_d == 4)
+      hipLaunchKernelGGL((gemm_chain_bf16x3_kernel<false, true, 4>), grid, dim3(256), smem, stream, d);
+    else
+      hipLaunchKernelGGL((gemm_chain_bf16x3_kernel<false, true, 9>), grid, dim3(256), smem, stream, d);
+  } else if (any_pre) {
     if (emb) AA_CHAIN_LAUNCH(true, true); else AA_CHAIN_LAUNCH(true, false);
   } else {
     if (emb) AA_CHAIN_LAUNCH(false, true); else AA_CHAIN_LAUNCH(false, false);

@@ -400,6 +400,8 @@ struct StepPlan {
   bool gather;                          // deterministic force assembly over the transposed CSR (off: atomics)
   bool zero_gsh, zero_forces;           // the reverse pass accumulates into d Y / the forces: zeroed first
   bool pair_zbl;                        // ZBL pair potential: one launch behind the forward (energy only) or in edge_tail (force step)
+  bool mom0_in_chain;                   // layer-0 moments reverse: tp_mom_bwd_first stops after GM0 and the last reverse chain applies it to its own
+                                        // rows in its epilogue (d a_e never stored, the layer-0 slab of d Y written there)
   bool block;                           // one block of a blocked step (the ONE place that says so; Runner reads it): only the block's atoms get their
                                         // energy written; with forces dvec / vec rows go to the frame-wide arrays in the gather form (no atomics) and the
                                         // caller assembles the forces
@@ -462,6 +464,7 @@ static bool wide_one_tile_pass(const ModelPipeline& pipe, ForwardKind forward) {
 
 // The whole per-step decision, from the plan (`pipe`, `opt`, `c`: the configuration at the widened sizes), the step's inputs and
 // the CU count of the device (read only where wide_one_tile_pass says so) alone: no HIP call, no allocation.
+constexpr int64_t kMom0EpilogueEdges = int64_t(256) * 3 * 128;  // (see StepPlan::mom0_in_chain in choose_step)
 static StepPlan choose_step(const ModelPipeline& pipe, const aa_plan_options& opt, const aa_model_config& c, const StepInputs& in, int cus) {
   const int64_t n = in.atom_end - in.atom0;
   const bool two_layer_chains = pipe.chains() && c.num_layers == 2;
@@ -500,6 +503,15 @@ static StepPlan choose_step(const ModelPipeline& pipe, const aa_plan_options& op
                      : !(pipe.fold_lat0_reverse && c.num_layers == 2)                ? LatentReverse::TwoLayerChain
                      : (resident_shape && !opt.chain_staged_weights)                 ? LatentReverse::Resident
                                                                                      : LatentReverse::FoldedChain;
+
+  // ---- layer-0 moments reverse: its per-edge half in the epilogue of the last reverse chain ----
+  // Where the folded one-layer last chain with the embedding contraction runs behind the moments kernels (fp32, l_max <= 2: what the chain's
+  // epilogue is compiled for).  aa_plan_options.mom0_epilogue: 0 = from kMom0EpilogueEdges edges on, 1 = wherever it applies, 2 = never.
+  // The threshold is one resident round of the chain on the chip (256 CUs x 3 workgroups x 128 rows): what the form saves is HBM traffic,
+  // and a step with fewer rows than that is bound by launch latency, not by traffic.
+  const bool mom0_ok = in.with_forces && in.f32 && s.folded_first_stage() && pipe.tp == TpPath::Moments && pipe.chains() && pipe.embed_fused &&
+                       pipe.fold_embed_table && (pipe.chain_pair == 0 || pipe.chain_pair == 1) && c.num_scalar == 64;
+  s.mom0_in_chain = mom0_ok && opt.mom0_epilogue != 2 && (opt.mom0_epilogue == 1 || in.edges >= kMom0EpilogueEdges);
 
   // ---- operator kernels ----
   // split form (default): per-atom vectors through HBM, edge loops in lean kernels (tp_operator_fused: fused form)
@@ -1564,7 +1576,11 @@ static Workspace layout_workspace(const aa_model_plan* p, int64_t N, int64_t E, 
     for (int i = 0; i < c.latent_mlp_depth; ++i) w.g_lat_h[i] = take(Ez * c.latent_mlp_width);
     for (int l = 0; l < L; ++l) w.g_scal[l] = take(Ez * u);
     if (!p->pipe.env_moments()) w.g_envw = take(Ez * p->W);
-    if (p->pipe.env_moments()) w.g_aenv = take(Ez * size_t(std::max(S, c.latent_mlp_width)));
+    // (StepPlan::mom0_in_chain: the per-atom GM0 [N][D][64] of the layer-0 moments reverse lies here -- that form never writes d a_e -- so
+    //  the slot holds whichever is larger; the same for every step on the plan, whatever form it takes)
+    const bool gm0_here = p->pipe.tp == TpPath::Moments && p->pipe.chains() && p->pipe.embed_fused && p->pipe.fold_embed_table && es == 4;
+    if (p->pipe.env_moments())
+      w.g_aenv = take(std::max(Ez * size_t(std::max(S, c.latent_mlp_width)), gm0_here ? Nz * p->D * 64 : size_t(0)));
     w.g_w0 = take(Ez * p->W);
     if (L > 1 && p->pipe.chain_pair < 0) {
       w.g_tf[0] = take(Ez * u * dmax);
@@ -1899,15 +1915,20 @@ struct Runner {
     if (!prof) return AA_OK;
     char nm[32];
     int o = snprintf(nm, sizeof(nm), "gc");
-    double elems = 0, fl = 0;
+    double elems = 0, fl = 0, per_atom = 0;
     for (int i = 0; i < ca.nlayers; ++i) {
       if (o < 28) o += snprintf(nm + o, sizeof(nm) - o, "_%dx%d", ca.L[i].g.K, ca.L[i].g.N);
       elems += gemm_row_elems(ca.L[i].g, true);  // a is an empty list for use_prev layers (kept tile in registers)
       if (ca.L[i].a_mode == 2) elems += 2.0 * ca.L[i].g.a.s[0].n;  // (+ the add and z rows of the operand transform)
       fl += 2.0 * double(E) * ca.L[i].g.K * ca.L[i].g.N;
+      if (ca.L[i].mom_gm0) {  // moments epilogue: + h, Y and d Y rows, the GM0 block of every atom once, two rank-D updates per row
+        elems += 64 + 2.0 * ca.L[i].mom_d;
+        per_atom += 64.0 * ca.L[i].mom_d;
+        fl += 4.0 * double(E) * ca.L[i].mom_d * 64;
+      }
     }
     (void)tag;
-    return mark(nm, elems, 0, fl);
+    return mark(nm, elems, per_atom, fl);
   }
 
   TpMomArgs mom_args(const aa_graph* g) const {
@@ -2748,6 +2769,12 @@ struct Runner {
         // (after a fused forward the embedding's slot holds a_e = silu(h) of scalar_embed_mlp and the env weights are folded behind
         //  its output layer, fold_embed_output: d a_e comes out instead of d emb)
         if (sp.folded_first_stage()) m.wt0 = wt(p->blob.o_wt0f);
+        if (sp.mom0_in_chain) {
+          // stops after GM0 (in the slot of d a_e, which this form never writes): no read of a_e, no d a_e, no layer-0 slab of d Y here
+          m.gm0 = buf(w.g_aenv);
+          if (int rc = launch_tp_mom_bwd_first_gm(p->pipe.chain_pair, m, stream)) return rc;
+          return mark("tp_mom_bwd_first", p->D + 2 * W + 2 * u + p->D, double(p->D) * 64, 2.0 * p->D * u);
+        }
         if (int rc = launch_tp_mom_bwd_first<T>(p->pipe.chain_pair, m, stream)) return rc;
         return mark("tp_mom_bwd_first", p->D + 2 * W + 2 * u + 2 * m.ka0 + 2 * p->D, 2.0 * p->D * u);
       }
@@ -2858,6 +2885,19 @@ struct Runner {
       // d h = ((d[two-body | w0] @ (W1 G0)^T) + d a_e of the moments) x silu'(h) -- ONE 256 -> 64 layer, 8 steps -- ...
       ca.nlayers = 1;
       ca.L[0] = chain_layer(E, in, 0, wt(p->blob.o_g0tfq), p->blob.ng0, 64, cn, nullptr, &zz, &ad, 0, 0, 0);
+      if (sp.mom0_in_chain) {
+        // ... with d a_e of the moments formed in the epilogue from GM0 of the row's center atom (tp_mom_bwd_first stopped there), which
+        // also writes the layer-0 slab of d Y: the silu'(h) factor and the addend are the epilogue's own
+        ca.L[0] = chain_layer(E, in, 0, wt(p->blob.o_g0tfq), p->blob.ng0, 64, cn, nullptr, nullptr, nullptr, 0, 0, 0);
+        ca.L[0].mom_gm0 = buf(w.g_aenv);
+        ca.L[0].mom_d = p->D;
+        ca.L[0].mom_y = buf(w.sh);
+        ca.L[0].ld_mom_y = p->D;
+        ca.L[0].mom_h = buf(w.se_h[0]);
+        ca.L[0].ld_mom_h = 64;
+        ca.L[0].mom_dy = buf(w.g_sh) + size_t(E) * p->D;
+        ca.L[0].ld_mom_dy = p->D;
+      }
       if (p->pipe.embed_fused && p->pipe.fold_embed_table) {
         // ... contracted against the folded two-body table in its epilogue
         contract_embedding(ca.L[0], wt(p->blob.o_embtab_h));
@@ -3336,6 +3376,13 @@ extern "C" int aa_model_debug_tap(const aa_model_plan* plan, const char* name, i
   } else if (n == "dvec" && with_forces) {  // [E,4] dE/dr_e
     *ptr = base + w.dvec;
     *ld = 4;
+  } else if (n == "gsh_env0" && with_forces && plan->pipe.channel_minor() && plan->pipe.tp_op < 0 && plan->cfg.num_layers >= 1) {
+    // [E,D] layer-0 env slab of d Y (slot 1 of g_sh): tp_mom_bwd_first, or the last reverse chain under StepPlan::mom0_in_chain
+    *ptr = base + w.g_sh + size_t(E) * plan->D * plan->esize();
+    *ld = plan->D;
+  } else if (n == "trev" && with_forces && plan->pipe.embed_fused) {  // [E,8] d E / d (the 8 basis functions), last reverse chain
+    *ptr = base + w.trev;
+    *ld = 8;
   } else {
     return fail(AA_ERR_INVALID, "aa_model_debug_tap: unknown tap");
   }

@@ -1243,7 +1243,10 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 && Sig0::LMAX <= 2) ? (KA2 ? 3
                               ma.ld_ga, static_cast<T*>(a.gsh_env), a.ld_gsh);
 }
 
-template <class Sig0, class Sig1, typename T, bool KA2>
+// GM_ONLY: the form that stops after GM0 -- pass 1, the per-atom contractions and the transposed env projection as in the two-pass
+// form, then GM0[atom][j][k] (already scaled by sf) goes to TpMomArgs::gm0 and the kernel returns: no second edge loop, no d a_e and
+// no layer-0 slab of d Y.  The last reverse chain applies GM0 to its own rows (ChainLayer::mom_gm0, aa_gemm.hip).
+template <class Sig0, class Sig1, typename T, bool KA2, bool GM_ONLY = false>
 #ifndef AA_MOM_FIRST_WAVES
 #define AA_MOM_FIRST_WAVES 2  // waves per SIMD the register budget is sized for (A/B: 3 = 168 VGPRs)
 #endif
@@ -1357,6 +1360,18 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 && Sig0::LMAX <= 2) ? AA_MOM_F
   const T sf = T(a.sf);
 #pragma unroll
   for (int j = 0; j < D; ++j) g2acc[j] *= sf;
+  if constexpr (GM_ONLY) {
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < D; ++j) sG[j * 64 + lane] = g2acc[j];
+    __builtin_amdgcn_wave_barrier();
+    T gm[D];
+    mom_gm_plain<T, D, R>(sG, static_cast<const T*>(ma.wt0), ma.ka0, 0, lane, gm);
+    T* out = static_cast<T*>(ma.gm0) + atom * D * 64 + lane;
+#pragma unroll
+    for (int j = 0; j < D; ++j) out[int64_t(j) * 64] = gm[j];
+    return;
+  }
   mom_backward_edges<T, D, R, KA2, false>(sh, a.ld_sh, static_cast<const T*>(ma.a0), ma.ld_a0, ma.ka0, false, g2acc,
                               static_cast<const T*>(ma.wt0), beg, end, lane, sG, sY, staged_cb, static_cast<T*>(ma.g_a),
                               ma.ld_ga, static_cast<T*>(a.gsh_env), a.ld_gsh);
@@ -1492,6 +1507,25 @@ AA_MOM_LAUNCHER(tp_mom_fwd_first, cg::Sig1, cg::Sig5, cg::Sig9)
 AA_MOM_LAUNCHER(tp_mom_fwd_last, cg::Sig1 AA_COMMA cg::Sig0, cg::Sig5 AA_COMMA cg::Sig4, cg::Sig9 AA_COMMA cg::Sig8)
 AA_MOM_LAUNCHER(tp_mom_bwd_last, cg::Sig1 AA_COMMA cg::Sig0, cg::Sig5 AA_COMMA cg::Sig4, cg::Sig9 AA_COMMA cg::Sig8)
 AA_MOM_LAUNCHER(tp_mom_bwd_first, cg::Sig1 AA_COMMA cg::Sig0, cg::Sig5 AA_COMMA cg::Sig4, cg::Sig9 AA_COMMA cg::Sig8)
+
+// the GM_ONLY form of tp_mom_bwd_first (fp32, l_max <= 2, env inputs 64 wide: what the last reverse chain's moments epilogue takes)
+int launch_tp_mom_bwd_first_gm(int pair, const TpMomArgs& a, hipStream_t stream) {
+  if (a.c.N == 0 || a.c.N <= a.c.atom0) return AA_OK;
+  if (a.c.u != 64 || a.ka0 != 64 || a.ka1 != 64 || !a.gm0 || (pair != 0 && pair != 1))
+    return fail(AA_ERR_INVALID, "tp_mom_bwd_first_gm: needs u == 64, env-input widths of 64, l_max <= 2 and the GM0 array");
+  const int wpb = std::max(1, std::min(4, a.waves_per_block));
+  dim3 grid((unsigned)((a.c.N - a.c.atom0 + wpb - 1) / wpb));
+  const int dpair = pair == 0 ? 4 : 9;
+  TpMomArgs b = a;
+  b.ka_lds = 64;
+  const size_t smem = sizeof(float) * wpb * dpair * (b.ka_lds + 64 + kSegCap);
+  if (pair == 0)
+    hipLaunchKernelGGL((tp_mom_bwd_first_kernel<cg::Sig1, cg::Sig0, float, false, true>), grid, dim3(64 * wpb), smem, stream, b);
+  else
+    hipLaunchKernelGGL((tp_mom_bwd_first_kernel<cg::Sig5, cg::Sig4, float, false, true>), grid, dim3(64 * wpb), smem, stream, b);
+  AA_CHECK_HIP(hipGetLastError());
+  return AA_OK;
+}
 
 AA_CHAIN_LAUNCHER(tp_chain_fwd_last)
 AA_CHAIN_LAUNCHER(tp_chain_bwd_last)

@@ -314,6 +314,9 @@ typedef struct {
                              * size with the chain-only tail where a tail applies (A/B of the deep tail) */
   int32_t chain_staged_weights; /* one-layer reverse chains: 1 = the per-workgroup weight staging of the general chain kernel also where the
                                  * persistent form with LDS-resident weights applies (round 6; A/B, tests)                               */
+  int32_t mom0_epilogue;    /* layer-0 moments reverse behind a folded last reverse chain that contracts the embedding (fp32, l_max <= 2): its
+                             * per-edge half -- d a_e and the layer-0 slab of d Y -- in that chain's epilogue, tp_mom_bwd_first stopping after the
+                             * per-atom GM0: 0 = automatic (steps of at least 98 304 edges), 1 = wherever it applies, 2 = never (A/B, tests) */
 } aa_plan_options;
 
 /* AA_ERR_INVALID, with aa_last_error() naming the limit and the size asked for, for a configuration whose edge kernels could not be
